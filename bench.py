@@ -736,6 +736,35 @@ def run_tp_child(args, rank, world, D, dev) -> dict:
     return json.loads(line[-1]).get("tp", {"error": "child line has no tp object"})
 
 
+DUMP_BYTES = 64 << 20         # --dump-outputs: upper bound of all files one run writes
+DUMP_KV_ROWS = 128            # KV-cache sequence positions sampled per sample (every layer, K and V, all kv heads)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir: str, ctxs, rank: int, world: int) -> None:
+    """--dump-outputs: what the LAST timed step handed its caller, per sample in flight, as float32 .npy files:
+    logits_last (the whole fp32 [vocab] row) and kv_k / kv_v ([layers, rows, kv_width]: the KV cache the prefill wrote, at
+    DUMP_KV_ROWS sequence positions drawn once with DUMP_SEED; the whole cache of C3 is ~0.9 GB).  Names get _rank<r> with
+    several ranks and _sample<j> with several samples in flight; the rows shrink so that the run stays under DUMP_BYTES."""
+    n_sets = world * len(ctxs)
+    os.makedirs(out_dir, exist_ok=True)
+    for j, c in enumerate(ctxs):
+        torch.cuda.synchronize()
+        S, L = c.res.seq_len, len(c.cache.k)
+        logits = c.res.logits_last.float().cpu().numpy()
+        row_bytes = 2 * L * c.cache.k[0].shape[1] * 4
+        n_rows = min(S, DUMP_KV_ROWS, (DUMP_BYTES // n_sets - logits.nbytes) // row_bytes)
+        if n_rows < 1:
+            raise SystemExit(f"--dump-outputs: {n_sets} samples do not fit {DUMP_BYTES >> 20} MB")
+        rows = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(S, size=n_rows, replace=False))).to(c.cache.k[0].device)
+        tag = (f"_rank{rank}" if world > 1 else "") + (f"_sample{j}" if len(ctxs) > 1 else "")
+        arrays = {"logits_last": logits,
+                  "kv_k": torch.stack([k[rows] for k in c.cache.k]).float().cpu().numpy(),
+                  "kv_v": torch.stack([v[rows] for v in c.cache.v]).float().cpu().numpy()}
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, f"{name}{tag}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -777,7 +806,14 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-tp", action="store_true", help="N > 1: skip the additional one-sample-on-all-ranks (strong scaling) measurement")
     ap.add_argument("--tp-timeout", type=float, default=150.0, help="watchdog of the additional tensor-parallel measurement, seconds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (last-position logits + a fixed sample of the KV "
+                         "cache it wrote) as DIR/<name>.npy, for output-by-output comparison of two builds (llava-c3, --parallelism sample)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.workload != "llava-c3" or args.parallelism != "sample"):
+        raise SystemExit("--dump-outputs is implemented for the llava-c3 workload with --parallelism sample")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -886,7 +922,7 @@ def main():
             with torch.cuda.stream(c.stream):
                 c.cache.length = 0
                 tiles = gpu_tiler.tile_sample(c.raw)[0] if with_tiler else c.tiles
-                out = eng.prefill(c.ids, tiles, cache=c.cache)
+                out = c.res = eng.prefill(c.ids, tiles, cache=c.cache)
         return out
 
     def barrier():
@@ -906,6 +942,8 @@ def main():
         assert r.seq_len == S and torch.isfinite(r.logits_last).all()
         return el, r
     elapsed, res = timed(args.warmup, args.steps)
+    if args.dump_outputs:                                          # before anything else runs on these caches
+        dump_outputs(args.dump_outputs, ctxs, rank, world)
     ms_per_step = elapsed / args.steps * 1e3
     # the same step from ready-made tiles (what round 1 timed): the tiler's share of the headline
     n_ex = max(2, min(args.steps, 5))

@@ -125,3 +125,40 @@ def test_library_load_imports_torch_first():
             "print('ok')\n")
     r = subprocess.run([sys.executable, "-c", code], cwd=repo, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+
+
+def test_dump_outputs_writes_the_last_step_within_the_size_bound(monkeypatch, tmp_path):
+    """--dump-outputs: float32 logits + a fixed seeded sample of the KV cache of every sample in flight, the same rows from run to run,
+    under DUMP_BYTES at the C3 shape (32 layers, 8 kv heads x 128, S = 7187, vocab 128256) and with several samples in flight."""
+    import os
+
+    import numpy as np
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    S, L, w, V = 7187, 32, 1024, 128256
+
+    def ctx(seed):
+        g = torch.Generator().manual_seed(seed)
+        c = types.SimpleNamespace(cache=types.SimpleNamespace(k=[torch.randn(S, w, generator=g).half() for _ in range(L)],
+                                                             v=[torch.randn(S, w, generator=g).half() for _ in range(L)]))
+        c.res = types.SimpleNamespace(seq_len=S, logits_last=torch.randn(V, generator=g))
+        return c
+
+    one = [ctx(0)]
+    bench.dump_outputs(str(tmp_path / "a"), one, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), one, 0, 1)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["kv_k.npy", "kv_v.npy", "logits_last.npy"]
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    k = np.load(tmp_path / "a" / "kv_k.npy")
+    assert k.shape == (L, bench.DUMP_KV_ROWS, w)
+    assert np.array_equal(np.load(tmp_path / "a" / "logits_last.npy"), one[0].res.logits_last.numpy())
+    rows = [int(np.flatnonzero((one[0].cache.k[0].float().numpy() == k[0, i]).all(1))[0]) for i in range(3)]
+    assert rows == sorted(rows) and all(r < S for r in rows)              # rows of the written cache, in sequence order
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BYTES
+    many = [ctx(s) for s in range(4)]
+    bench.dump_outputs(str(tmp_path / "c"), many, 1, 2)                  # rank 1 of 2, four samples in flight: 8 sets in one run
+    names = sorted(os.listdir(tmp_path / "c"))
+    assert len(names) == 12 and "kv_v_rank1_sample3.npy" in names
+    assert 2 * sum(os.path.getsize(tmp_path / "c" / f) for f in names) <= bench.DUMP_BYTES

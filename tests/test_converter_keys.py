@@ -1,34 +1,24 @@
 """f1: the tensor names leopard_amd reads from a checkpoint are exactly the names the reference's converter
 writes (toolkits/model_checkpoints_convertor/llava/hf2megatron_llava.py: the megatron -> HF direction, name map :168-175,
-LLM layers :1150-1300, vision / projector / embeddings :1309-1455).  The converter's source is parsed for the string
-fragments it assembles keys from — nothing is executed (it imports megatron) and nothing is copied.  Runs only where
-/root/reference exists (the build container)."""
+LLM layers :1150-1300, vision / projector / embeddings :1309-1455).  The string fragments the converter assembles keys
+from, and its q / k / v index map, are stored data (tests/golden/converter_keys.json, written by oracle/gen_converter_keys.py,
+which parses the converter's source without executing it)."""
+import json
 import os
 import re
 
-import pytest
 
-CONV = "/root/reference/Pai-Megatron-Patch/toolkits/model_checkpoints_convertor/llava/hf2megatron_llava.py"
-pytestmark = pytest.mark.skipif(not os.path.exists(CONV), reason="reference tree not present (GPU box)")
-
-
-def test_engine_reads_exactly_the_converter_key_set():
+def test_engine_reads_exactly_the_converter_key_set(golden_dir):
     from leopard_amd.config import full_config
     from leopard_amd.synth import param_specs
-    import io
-    import tokenize
-    src = open(CONV).read()
-    lit = set()
-    for tok in tokenize.generate_tokens(io.StringIO(src).readline):          # every string literal of the file, f-strings as written
-        if tok.type == tokenize.STRING:
-            body = re.sub(r"^[rbfuRBFU]*", "", tok.string)
-            q = body[:3] if body[:3] in ('"""', "'''") else body[:1]
-            lit.add(body[len(q):-len(q)])
+    with open(os.path.join(golden_dir, "converter_keys.json")) as f:
+        fx = json.load(f)
+    lit = set(fx["name_literals"])
     # fragments of the name map (:168-175) and of the vision branch (:1309-1416)
     llm_ops = {".self_attn.o_proj.", ".mlp.gate_proj.", ".mlp.up_proj.", ".mlp.down_proj.", ".input_layernorm.", ".post_attention_layernorm."}
     assert llm_ops <= lit
     assert "language_model.model.layers.{layer_idx}" in lit and ".self_attn.{QKV[index]}.weight" in lit
-    assert re.search(r"QKV = \{0: 'q_proj', 1: 'k_proj', 2: 'v_proj'\}", src)
+    assert fx["qkv_index_map"] == ["q_proj", "k_proj", "v_proj"]
     vit_prefix = "vision_tower.vision_model.encoder.layers."
     vit_suffix = {".self_attn.out_proj.weight", ".self_attn.out_proj.bias", ".mlp.fc1.weight", ".mlp.fc1.bias", ".mlp.fc2.weight",
                   ".mlp.fc2.bias", ".layer_norm1.weight", ".layer_norm1.bias", ".layer_norm2.weight", ".layer_norm2.bias"}

@@ -11,6 +11,8 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from leopard_amd import dist as D
+
 pytestmark = pytest.mark.gpu
 
 
@@ -236,33 +238,101 @@ def test_tensor_parallel_c2_full_depth_vs_oracle_fixture_and_tp_checkpoint_load(
     assert d <= 2.5e-3
 
 
-def _worker_c2_tp8(rank, world, port, out):
+class GlooThreadComm(D.Comm):
+    """Host-staged gloo collectives for one rank of a group whose ranks are THREADS of one process (their own ProcessGroupGloo each, over
+    a shared in-memory store): the same gloo algorithms and reduce order as TorchComm over a gloo default group, for tests that need more
+    ranks than processes may hold the device at once.  Matches TorchComm's staging: the copies run on ``stream`` (or the current one)."""
+
+    def __init__(self, store, rank, world, timeout_s=1800):
+        import datetime
+        self._pg = torch.distributed.ProcessGroupGloo(store, rank, world, datetime.timedelta(seconds=timeout_s))
+        self.rank, self.world, self.backend, self.sent_bytes = rank, world, "gloo (one thread per rank)", 0
+
+    def _collective(self, stream, t, out, run):
+        """Stage ``t`` through the host, run the collective on the host copy, copy the result into ``out`` on the device."""
+        with D.TorchComm._on(stream):
+            h_in = t.cpu().contiguous()
+            h_out = run(h_in)
+            out.copy_(h_out)
+
+    def all_gather(self, out, inp, stream=None):
+        self._count("ag", inp)
+        def run(h):
+            o = torch.empty(out.shape, dtype=out.dtype)
+            self._pg._allgather_base(o, h).wait()
+            return o
+        self._collective(stream, inp, out, run)
+
+    def reduce_scatter(self, out, inp, stream=None):
+        self._count("rs", inp)
+        def run(h):
+            o = torch.empty(out.shape, dtype=out.dtype)
+            self._pg._reduce_scatter_base(o, h).wait()
+            return o
+        self._collective(stream, inp, out, run)
+
+    def all_reduce(self, t, stream=None):
+        self._count("ar", t)
+        def run(h):
+            self._pg.allreduce([h]).wait()
+            return h
+        self._collective(stream, t, t, run)
+
+    def broadcast(self, t, root, stream=None):
+        def run(h):
+            self._pg.broadcast(h, root).wait()
+            return h
+        self._collective(stream, t, t, run)
+
+    def barrier(self):
+        self._pg.allreduce([torch.zeros(1)]).wait()
+
+
+def _rank_thread_c2_tp8(rank, world, store, results):
     """C2 at FULL depth on EIGHT ranks sharing one device (1/8 of the LLM per rank): the 8-way reduce-scatter order, the 8-way column split of the
-    head, and the tile-sharded vision encode with 7 ViT inputs on 8 ranks — one rank has nothing to encode."""
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    from leopard_amd import dist as D
-    from leopard_amd.config import full_config
-    from leopard_amd.engine import LeopardEngine
-    from leopard_amd.ops import Ops
-    from leopard_amd.weights import EngineWeights, SynthSource
-    from tests.test_gpu_parity import sample_inputs
-    dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    D.init(backend="gloo")
-    ops, cfg, dtype = Ops(), full_config(), torch.float16
-    eng = LeopardEngine(cfg, EngineWeights.build(cfg, SynthSource(cfg, ops, dev, dtype), dtype, tp_rank=rank, tp_size=world), ops=ops, device=dev)
-    u8, ids, _ = sample_inputs(cfg, 1, 1344, 896)
-    tiles = torch.from_numpy(u8).to(dev)
-    assert tiles.shape[0] == 7 and world == 8
-    res = {}
-    eng.tp_chunks, eng.tp_comm_dtype = 2, torch.float32
-    res["fast, fp32 reduce-scatter"] = eng.prefill(ids, tiles).logits_last.float().cpu()
-    eng.precision = "lo4"
-    res["lo4, fp32 reduce-scatter"] = eng.prefill(ids, tiles).logits_last.float().cpu()
-    shard = (eng.W.llm_layers[0].o_w.shape, eng.W.lm_head.shape[0])
-    torch.cuda.synchronize()
-    out.put((rank, {k: v.tolist() for k, v in res.items()}, shard))
-    D.barrier()
+    head, and the tile-sharded vision encode with 7 ViT inputs on 8 ranks — one rank has nothing to encode.  One thread per rank, each on its
+    own stream, as one process per rank would have."""
+    try:
+        from leopard_amd.config import full_config
+        from leopard_amd.engine import LeopardEngine
+        from leopard_amd.ops import Ops
+        from leopard_amd.weights import EngineWeights, SynthSource
+        from tests.test_gpu_parity import sample_inputs
+        dev = torch.device("cuda:0")
+        torch.cuda.set_device(dev)
+        comm = GlooThreadComm(store, rank, world)
+        with torch.cuda.stream(torch.cuda.Stream(device=dev)):
+            ops, cfg, dtype = Ops(), full_config(), torch.float16
+            eng = LeopardEngine(cfg, EngineWeights.build(cfg, SynthSource(cfg, ops, dev, dtype), dtype, tp_rank=rank, tp_size=world), ops=ops,
+                                device=dev, comm=comm)
+            u8, ids, _ = sample_inputs(cfg, 1, 1344, 896)
+            tiles = torch.from_numpy(u8).to(dev)
+            assert tiles.shape[0] == 7 and world == 8
+            res = {}
+            eng.tp_chunks, eng.tp_comm_dtype = 2, torch.float32
+            res["fast, fp32 reduce-scatter"] = eng.prefill(ids, tiles).logits_last.float().cpu()
+            eng.precision = "lo4"
+            res["lo4, fp32 reduce-scatter"] = eng.prefill(ids, tiles).logits_last.float().cpu()
+            shard = (eng.W.llm_layers[0].o_w.shape, eng.W.lm_head.shape[0])
+            torch.cuda.synchronize()
+        results[rank] = (rank, {k: v.tolist() for k, v in res.items()}, shard)
+        comm.barrier()
+    except BaseException as e:                                   # noqa: BLE001  (reported by _worker_c2_tp8)
+        results[rank] = e
+
+
+def _worker_c2_tp8(world, out):
+    """The eight ranks as threads of this ONE process: eight processes on the device would be more than a shared machine allows."""
+    import threading
+    store = torch.distributed.HashStore()
+    results = {}
+    threads = [threading.Thread(target=_rank_thread_c2_tp8, args=(r, world, store, results)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    errs = [repr(v) for v in results.values() if isinstance(v, BaseException)]
+    out.put(("error", errs) if errs or len(results) != world else ("ok", [results[r] for r in range(world)]))
 
 
 def test_tensor_parallel_c2_full_depth_eight_ranks_one_gpu():
@@ -273,14 +343,12 @@ def test_tensor_parallel_c2_full_depth_eight_ranks_one_gpu():
     mp.set_start_method("spawn", force=True)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_c2_tp8, args=(r, 8, port, q)) for r in range(8)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=2400) for _ in procs)
-    for p in procs:
-        p.join(timeout=180)
-        assert p.exitcode == 0
+    p = ctx.Process(target=_worker_c2_tp8, args=(8, q))
+    p.start()
+    status, res = q.get(timeout=2400)
+    p.join(timeout=180)
+    assert status == "ok", res
+    assert p.exitcode == 0 and len(res) == 8
     v0 = res[0][1]
     for r in res[1:]:
         assert r[1] == v0 and r[2] == res[0][2]                  # every rank holds the same logits and an equal shard

@@ -1,6 +1,5 @@
 """-m gpu: the eval-script-facing surfaces ON THE DEVICE (SURVEY.md 8 rows b, f1, f4) — the same objects the reference's scripts
-drive (tests/test_reference_cli_unmodified.py runs those scripts themselves in the build container; /root/reference does not
-exist on the GPU box):
+drive (the suite does not run the reference's scripts themselves: they are not part of this repository):
 
   * f1: a sharded safetensors checkpoint AND a sharded pytorch_model-*.bin checkpoint in the converter's key layout ->
         compat.from_pretrained(...).to('cuda:0') -> forward / generate vs the CPU oracle;
