@@ -354,6 +354,17 @@ int lmi_attn_decode_pool(const void* q, const void* k, const void* v, void* out,
 int lmi_decode_advance(const float* logits, int B, int vocab, int ld_logits, const int64_t* suppress, int n_suppress, int64_t* tok, int* pos,
                        int* k_len, int* live, int* budget, const int64_t* eos, int n_eos, int64_t* hist, int* hist_pos, int hist_len, void* stream);
 
+/* The SAMPLED form of lmi_decode_advance (same arguments, same history / stop rule / advance): tok[b] is drawn from softmax(logits[b] / T)
+ * restricted by top-k and top-p, in HF's warper order, with per-row device parameters temperature[b] (> 0), top_k[b] (0 = off),
+ * top_p[b] (>= 1 = off) and a counter-based RNG: Philox4x32-10 keyed by seed[b] at the counter (step[b], token index); step[b] += live[b].
+ * Kept set: a prefix of the order (scaled logit descending, lower index first on ties) — the first k tokens for top-k, the shortest
+ * prefix of those whose mass (exp(s - max s) in fp32, summed in 2^-32 fixed point) reaches ceil(top_p * their mass) for top-p, at least
+ * one token; the draw is Gumbel-max over the kept set.  A row's token depends only on its logits row, seed and step.  Exact rules:
+ * leopard_amd/csrc/sample.h. */
+int lmi_decode_sample(const float* logits, int B, int vocab, int ld_logits, const int64_t* suppress, int n_suppress, const float* temperature,
+                      const int* top_k, const float* top_p, const uint64_t* seed, int* step, int64_t* tok, int* pos, int* k_len, int* live,
+                      int* budget, const int64_t* eos, int n_eos, int64_t* hist, int* hist_pos, int hist_len, void* stream);
+
 /* RoPE (rotate-half; cos/sin fp32 [S, head_dim/2] built from position_ids and the llama3-scaled inverse
  * frequencies, rotary_pos_embedding.py:48-83,197-239) applied in place to the q and k heads of packed qkv rows
  * [S, ld]; when k_cache/v_cache are non-null also appends rotated K and V to the cache rows cache_pos0.. */

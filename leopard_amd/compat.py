@@ -26,6 +26,7 @@ from .config import LeopardConfig
 from .engine import KVCache, LeopardEngine
 from .ops import Ops
 from .weights import EngineWeights
+from . import sampling
 
 
 @dataclass
@@ -66,6 +67,8 @@ class LeopardForConditionalGeneration:
         self._ops = ops
         self._engine: Optional[LeopardEngine] = None
         self.device = torch.device("cpu")
+        self.generation_defaults: dict = {}              # do_sample / temperature / top_k / top_p of the checkpoint's generation_config.json
+        self.last_decoding = "greedy"                    # the decoding rule of the last generate* call (leopard_amd.sampling.describe)
 
     # ---- loading ---------------------------------------------------------------------------------------------
     @classmethod
@@ -75,8 +78,10 @@ class LeopardForConditionalGeneration:
         tensor-parallel shard ``tp_rank`` of the LLM — the checkpoint's tensors are sliced while they stream to the device
         (EngineWeights.build) — and needs an initialised process group of that size (leopard_amd.dist.init) by the time ``.to(device)`` runs."""
         cfg = load_config(path)
-        return cls(cfg, lambda dev, dt: CheckpointSource(path, dev, dt), compute_dtype, ops, torch_dtype=torch_dtype, precision=precision,
-                   tp_rank=tp_rank, tp_size=tp_size)
+        m = cls(cfg, lambda dev, dt: CheckpointSource(path, dev, dt), compute_dtype, ops, torch_dtype=torch_dtype, precision=precision,
+                tp_rank=tp_rank, tp_size=tp_size)
+        m.generation_defaults = sampling.read_generation_config(path)
+        return m
 
     def eval(self):
         return self
@@ -140,36 +145,52 @@ class LeopardForConditionalGeneration:
     __call__ = forward
 
     # ---- EVAL:448-452 ------------------------------------------------------------------------------------------
+    def _sampling(self, where: str, unused: dict, do_sample, temperature, top_k, top_p, seed):
+        """HF decoding arguments -> SamplingParams (None = greedy); unsupported options warn (leopard_amd.sampling)."""
+        sampling.warn_unsupported(where, unused)
+        sp = sampling.resolve(self.generation_defaults, do_sample, temperature, top_k, top_p, seed)
+        self.last_decoding = sampling.describe(sp)
+        return sp
+
     @torch.no_grad()
     def generate(self, input_ids, pixel_values=None, attention_mask=None, pad_token_id=None, eos_token_id=None,
-                 max_new_tokens: int = 128, use_cache: bool = True, **unused):
+                 max_new_tokens: int = 128, use_cache: bool = True, do_sample=None, temperature=None, top_k=None, top_p=None,
+                 seed: Optional[int] = None, **unused):
+        """Greedy (EVAL:448-452), or sampled with ``do_sample=True`` (temperature / top_k / top_p, HF semantics: leopard_amd.sampling)."""
+        sp = self._sampling("generate", unused, do_sample, temperature, top_k, top_p, seed)
         if input_ids.shape[0] != 1:
             raise NotImplementedError("batch 1 per call, as in the reference harness")
         eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
         tiles = self._as_tiles(pixel_values)
-        return self.engine.generate(input_ids.to(self.device), tiles, max_new_tokens=max_new_tokens, eos_token_id=eos)
+        return self.engine.generate(input_ids.to(self.device), tiles, max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp)
 
 
     @torch.no_grad()
     def generate_batch(self, requests: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], eos_token_id=None,
-                       max_new_tokens: int = 128, **unused) -> List[torch.Tensor]:
+                       max_new_tokens: int = 128, do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None,
+                       **unused) -> List[torch.Tensor]:
         """[(input_ids [1, S_in], pixel_values)] -> [LongTensor [1, S_in + T]]: the batched form of ``generate`` (one packed prefill
         for all requests, LeopardEngine.generate_batch).  Not a surface of the reference script — its loop is batch 1 — but of
-        leopard_amd.harness.run_inference(batch_size=...)."""
+        leopard_amd.harness.run_inference(batch_size=...).  Sampling: request i draws with its own seed (SamplingParams.for_request)."""
+        sp = self._sampling("generate_batch", unused, do_sample, temperature, top_k, top_p, seed)
         eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
         samples = [(ids.to(self.device), self._as_tiles(pix)) for ids, pix in requests]
-        return self.engine.generate_batch(samples, max_new_tokens=max_new_tokens, eos_token_id=eos)
+        return self.engine.generate_batch(samples, max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp)
 
 
     @torch.no_grad()
     def generate_stream(self, requests: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8, eos_token_id=None,
-                        max_new_tokens: int = 128, stats: Optional[dict] = None, **unused) -> List[torch.Tensor]:
+                        max_new_tokens: int = 128, stats: Optional[dict] = None, do_sample=None, temperature=None, top_k=None, top_p=None,
+                        seed: Optional[int] = None, **unused) -> List[torch.Tensor]:
         """Continuous batching over a list of requests: ``batch_size`` decode slots kept busy (LeopardEngine.generate_stream); the outputs
-        come back in request order, each what ``generate`` returns for that request."""
+        come back in request order, each what ``generate`` returns for that request.  Sampling: request i draws with its own seed
+        (SamplingParams.for_request), so its tokens do not depend on ``batch_size``."""
+        sp = self._sampling("generate_stream", unused, do_sample, temperature, top_k, top_p, seed)
         eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
         # a callable in place of the pixels is called when a slot admits the request (leopard_amd.harness: bounded memory over a shard)
         samples = [(ids.to(self.device), (lambda f=pix: self._as_tiles(f())) if callable(pix) else self._as_tiles(pix)) for ids, pix in requests]
-        return self.engine.generate_stream(samples, batch_size=batch_size, max_new_tokens=max_new_tokens, eos_token_id=eos, stats=stats)
+        return self.engine.generate_stream(samples, batch_size=batch_size, max_new_tokens=max_new_tokens, eos_token_id=eos, stats=stats,
+                                           sampling=sp)
 
 
 def from_pretrained(path: str, torch_dtype=torch.float32, **kw) -> LeopardForConditionalGeneration:

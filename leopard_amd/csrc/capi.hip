@@ -16,6 +16,7 @@
 #include "gemm.h"
 #include "lowbit.h"
 #include "skinny.h"
+#include "sample.h"
 
 using namespace lmi;
 
@@ -1491,6 +1492,23 @@ int lmi_decode_advance(const float* logits, int B, int vocab, int ld_logits, con
     a.B = B;
     LMI_LAUNCH(decode_advance_kernel, dim3(B), dim3(1024), 0, stream, a);
     return check_launch("lmi_decode_advance");
+}
+
+int lmi_decode_sample(const float* logits, int B, int vocab, int ld_logits, const int64_t* suppress, int n_suppress, const float* temperature,
+                      const int* top_k, const float* top_p, const uint64_t* seed, int* step, int64_t* tok, int* pos, int* k_len, int* live,
+                      int* budget, const int64_t* eos, int n_eos, int64_t* hist, int* hist_pos, int hist_len, void* stream) {
+    if (!logits || !tok || !pos || !temperature || !top_k || !top_p || !seed || !step || B < 0 || vocab <= 0 || ld_logits < vocab ||
+        n_suppress < 0 || (n_suppress && !suppress) || n_eos < 0 || (n_eos && !eos) || (hist && (!hist_pos || hist_len <= 0)))
+        return fail(LMI_EINVAL, "lmi_decode_sample: bad argument");
+    if (B == 0) return LMI_OK;
+    DecodeSampleArgs a;
+    DecodeAdvanceArgs& d = a.adv;
+    d.logits = logits; d.vocab = vocab; d.ld_logits = ld_logits; d.suppress = suppress; d.n_suppress = n_suppress; d.tok = tok; d.pos = pos;
+    d.k_len = k_len; d.live = live; d.budget = budget; d.eos = eos; d.n_eos = n_eos; d.hist = hist; d.hist_pos = hist_pos; d.hist_len = hist_len;
+    d.B = B;
+    a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.step = step;
+    LMI_LAUNCH(decode_sample_kernel, dim3(B), dim3(1024), 0, stream, a);
+    return check_launch("lmi_decode_sample");
 }
 
 int lmi_gemv(const void* W, const void* x, const float* bias, void* out, int N, int K, int ldw, int epilogue, int dtype,

@@ -486,6 +486,25 @@ struct DecodeAdvanceArgs {
     int* hist_pos;            // [B] per-sequence step counter of the ring
     int hist_len, B;
 };
+// what follows the choice of token bi for sequence b (one thread): token write, history ring, stop rule, position / key-count advance
+// (shared with decode_sample_kernel, sample.h)
+LMI_DEV void decode_advance_tail(const DecodeAdvanceArgs& a, int b, int bi) {
+    a.tok[b] = bi;
+    int lv = a.live ? a.live[b] : 1;
+    if (a.hist) {
+        const int hp = a.hist_pos[b];
+        a.hist[(long)(hp % a.hist_len) * a.B + b] = bi;
+        a.hist_pos[b] = hp + 1;
+    }
+    int bud = 1;
+    if (a.budget) { bud = a.budget[b] - lv; a.budget[b] = bud; }
+    bool stop = bud <= 0;
+    for (int j = 0; j < a.n_eos; ++j) stop = stop || (a.eos[j] == (int64_t)bi);
+    if (stop) lv = 0;
+    if (a.live) a.live[b] = lv;
+    a.pos[b] += lv;
+    if (a.k_len) a.k_len[b] += lv;
+}
 __global__ void __launch_bounds__(1024) decode_advance_kernel(DecodeAdvanceArgs a) {
     __shared__ float best_v[16];
     __shared__ int best_i[16];
@@ -532,21 +551,7 @@ __global__ void __launch_bounds__(1024) decode_advance_kernel(DecodeAdvanceArgs 
         for (int w = 1; w < nw; ++w)
             if (best_v[w] > bv || (best_v[w] == bv && best_i[w] < bi)) { bv = best_v[w]; bi = best_i[w]; }
         if (bi == 0x7fffffff) bi = 0;                               // a row of NaN / -inf only
-        a.tok[b] = bi;
-        int lv = a.live ? a.live[b] : 1;
-        if (a.hist) {
-            const int hp = a.hist_pos[b];
-            a.hist[(long)(hp % a.hist_len) * a.B + b] = bi;
-            a.hist_pos[b] = hp + 1;
-        }
-        int bud = 1;
-        if (a.budget) { bud = a.budget[b] - lv; a.budget[b] = bud; }
-        bool stop = bud <= 0;
-        for (int j = 0; j < a.n_eos; ++j) stop = stop || (a.eos[j] == (int64_t)bi);
-        if (stop) lv = 0;
-        if (a.live) a.live[b] = lv;
-        a.pos[b] += lv;
-        if (a.k_len) a.k_len[b] += lv;
+        decode_advance_tail(a, b, bi);
     }
 }
 

@@ -91,6 +91,36 @@ class KVCache:
         self.capacity, self.length = capacity, 0
 
 
+@dataclass
+class SamplingParams:
+    """Sampled decoding (lmi_decode_sample, csrc/sample.h): temperature, then top-k (0 = off), then top-p (1.0 = off); the draws of a
+    request are Philox4x32-10 keyed by ``seed``, one counter step per produced token (step 0 = the token from the prefill's logits)."""
+    temperature: float = 1.0
+    top_k: int = 50
+    top_p: float = 1.0
+    seed: int = 0
+
+    def __post_init__(self):
+        if not self.temperature > 0:
+            raise ValueError(f"temperature must be > 0 when sampling, got {self.temperature}")
+        if int(self.top_k) < 0:
+            raise ValueError(f"top_k must be >= 0, got {self.top_k}")
+        if not 0.0 <= float(self.top_p) <= 1.0:
+            raise ValueError(f"top_p must be in [0, 1], got {self.top_p}")
+        self.seed = int(self.seed) & ((1 << 64) - 1)
+
+    def for_request(self, i: int) -> "SamplingParams":
+        """The parameters of request i of a call: its seed depends on the call's seed and i only (not on batch size or admission order)."""
+        return SamplingParams(self.temperature, self.top_k, self.top_p, (self.seed + i * 0x9E3779B97F4A7C15) & ((1 << 64) - 1))
+
+    def describe(self) -> str:
+        return f"sample(temperature={self.temperature:g}, top_k={int(self.top_k)}, top_p={self.top_p:g})"
+
+
+def _signed64(v: int) -> int:
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
 class LeopardEngine:
     def __init__(self, cfg: LeopardConfig, weights: EngineWeights, ops: Optional[Ops] = None, device=None,
                  use_tr: bool = True, comm=None, pack_llm_weights: Optional[bool] = None):
@@ -1233,6 +1263,7 @@ class LeopardEngine:
         st.cos, st.sin = self.rope_tables(torch.arange(cache.capacity))
         st.ws = torch.empty(self.ops.decode_workspace_elems(1, H, hd, cache.capacity), dtype=torch.float32, device=dev)
         st.graph = None
+        self._sampling_buffers(st, 1)
         st.layout = self.llm_packed                                   # a captured step replays the launches of the weight layout it was captured on
         st.mode = (self.precision, self.decode_precision)             # ... and of the precision mode
         cache._decode_state = st
@@ -1260,7 +1291,7 @@ class LeopardEngine:
                                 lambda i: ops.attention_decode(st.qkv[:, :qw], cache.k[i], cache.v[i], st.att, st.cu_q, st.cu_k, 1, cache.capacity, H, KV,
                                                                hd, hd ** -0.5, st.ws, window=tc.sliding_window or 0, hl=st.hl))
             ops.lm_head_last(W.lm_head, st.x, None, W.final_norm, tc.rms_norm_eps, st.logits.view(1, -1))
-            ops.decode_advance(st.logits.view(1, -1), tc.vocab_size, st.tok, st.pos, k_len=st.cu_k[1:], suppress=self.suppress_tokens)
+            self._choose(st, st.logits.view(1, -1), k_len=st.cu_k[1:])
             return
         fuse = tc.hidden_size == 4096                 # lmi_gemv_rmsnorm: the norm rides in the projection's launch
         for i, L in enumerate(W.llm_layers):
@@ -1284,8 +1315,54 @@ class LeopardEngine:
                 ops.gemv(L.gu_w, st.h[0], st.gu[0], epilogue=3)
             row_parallel(L.down_w, st.gu[0])
         ops.lm_head_last(W.lm_head, st.x, None, W.final_norm, tc.rms_norm_eps, st.logits.view(1, -1))
-        # greedy choice and position / key-count advance stay on the device, one launch (lmi_decode_advance; capturable)
-        ops.decode_advance(st.logits.view(1, -1), tc.vocab_size, st.tok, st.pos, k_len=st.cu_k[1:], suppress=self.suppress_tokens)
+        # greedy (or sampled) choice and position / key-count advance stay on the device, one launch (lmi_decode_advance /
+        # lmi_decode_sample; capturable)
+        self._choose(st, st.logits.view(1, -1), k_len=st.cu_k[1:])
+
+    def _sampling_buffers(self, st, B: int) -> None:
+        """Per-row sampling parameters of a decode state, in device memory: written before a replay, read by the captured step, so new
+        parameters never need a new capture.  ``st.sampling`` selects which of the two captured steps runs (``graph`` / ``graph_s``)."""
+        dev = self.device
+        st.sampling = False
+        st.graph_s = None
+        st.temp = torch.ones(B, dtype=torch.float32, device=dev)
+        st.topk = torch.zeros(B, dtype=torch.int32, device=dev)
+        st.topp = torch.ones(B, dtype=torch.float32, device=dev)
+        st.seed = torch.zeros(B, dtype=torch.int64, device=dev)
+        st.step = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def _set_sampling(self, st, j: int, sp: "SamplingParams", step: int = 1) -> None:
+        """Row j of a decode state draws with ``sp`` from counter ``step`` on (the token from the prefill was step 0)."""
+        vals = torch.tensor([float(sp.temperature), float(sp.top_p)], dtype=torch.float32)
+        ints = torch.tensor([int(sp.top_k), int(step)], dtype=torch.int32)
+        st.temp[j:j + 1].copy_(vals[0:1]); st.topp[j:j + 1].copy_(vals[1:2])
+        st.topk[j:j + 1].copy_(ints[0:1]); st.step[j:j + 1].copy_(ints[1:2])
+        st.seed[j:j + 1].copy_(torch.tensor([_signed64(sp.seed)], dtype=torch.int64))
+
+    def _choose(self, st, logits, **kw) -> None:
+        """The tail of a decode step: lmi_decode_advance (greedy) or lmi_decode_sample (st.sampling) — the only difference between the two
+        captured steps."""
+        V = self.cfg.text_config.vocab_size
+        if st.sampling:
+            self.ops.decode_sample(logits, V, st.temp, st.topk, st.topp, st.seed, st.step, st.tok, st.pos, suppress=self.suppress_tokens, **kw)
+        else:
+            self.ops.decode_advance(logits, V, st.tok, st.pos, suppress=self.suppress_tokens, **kw)
+
+    def sample_first(self, logits: torch.Tensor, params: Sequence["SamplingParams"]) -> List[int]:
+        """The first token of each request from its prefill logits row ([n, >= vocab] or [vocab]) through lmi_decode_sample at step 0
+        (the sampled counterpart of ``first_token``)."""
+        rows = logits.reshape(-1, logits.shape[-1]).float()
+        n, dev = rows.shape[0], rows.device
+        temp = torch.tensor([float(p.temperature) for p in params], dtype=torch.float32).to(dev)
+        topk = torch.tensor([int(p.top_k) for p in params], dtype=torch.int32).to(dev)
+        topp = torch.tensor([float(p.top_p) for p in params], dtype=torch.float32).to(dev)
+        seed = torch.tensor([_signed64(p.seed) for p in params], dtype=torch.int64).to(dev)
+        step = torch.zeros(n, dtype=torch.int32, device=dev)
+        tok = torch.zeros(n, dtype=torch.int64, device=dev)
+        pos = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.ops.decode_sample(rows, min(self.cfg.text_config.vocab_size, rows.shape[1]), temp, topk, topp, seed, step, tok, pos,
+                               suppress=self.suppress_tokens)
+        return [int(t) for t in tok.tolist()]
 
     def _decode_run(self, st, cache: KVCache):
         # Tensor parallel: the step holds 2 all-reduces per layer.  Through RcclComm they are plain stream-ordered RCCL launches, which
@@ -1294,20 +1371,21 @@ class LeopardEngine:
         # CPU tests, host-staged) it cannot be captured and runs eagerly.
         from .dist import RcclComm
         if getattr(st, "layout", self.llm_packed) != self.llm_packed:      # pack_llm_weights / unpack_llm_weights since the capture
-            st.graph, st.layout = None, self.llm_packed
+            st.graph, st.graph_s, st.layout = None, None, self.llm_packed
+        gname = "graph_s" if st.sampling else "graph"                      # greedy and sampled steps: one captured graph each
         tp_capturable = self.tp_size == 1 or (isinstance(self.comm, RcclComm) and self.tp_decode_graph)
         if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs or not tp_capturable or getattr(st, "graph_failed", False):
             self._decode_body(st, cache)
             return
-        if st.graph is None:
+        if getattr(st, gname) is None:
             # warm-up outside capture (first-use attribute calls, allocator), on copies of the device counters
-            keep = (st.tok.clone(), st.pos.clone(), st.cu_k.clone())
+            keep = (st.tok.clone(), st.pos.clone(), st.cu_k.clone(), st.step.clone())
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(side):
                 self._decode_body(st, cache)
             torch.cuda.current_stream(self.device).wait_stream(side)
-            st.tok.copy_(keep[0]); st.pos.copy_(keep[1]); st.cu_k.copy_(keep[2])
+            st.tok.copy_(keep[0]); st.pos.copy_(keep[1]); st.cu_k.copy_(keep[2]); st.step.copy_(keep[3])
             sent0 = self.comm.sent_bytes if self.comm is not None else 0
             try:
                 g = torch.cuda.CUDAGraph()
@@ -1320,15 +1398,15 @@ class LeopardEngine:
                 warnings.warn(f"tensor-parallel decode step could not be captured in a HIP graph ({exc}); running it eagerly")
                 st.graph_failed = True
                 torch.cuda.synchronize(self.device)
-                st.tok.copy_(keep[0]); st.pos.copy_(keep[1]); st.cu_k.copy_(keep[2])
+                st.tok.copy_(keep[0]); st.pos.copy_(keep[1]); st.cu_k.copy_(keep[2]); st.step.copy_(keep[3])
                 self._decode_body(st, cache)
                 return
             st.graph_comm_bytes = (self.comm.sent_bytes - sent0) if self.comm is not None else 0    # what one replay puts on the links
             if self.comm is not None:
                 self.comm.sent_bytes = sent0           # capture records, it does not send
-            st.tok.copy_(keep[0]); st.pos.copy_(keep[1]); st.cu_k.copy_(keep[2])      # capture does not execute
-            st.graph = g
-        st.graph.replay()
+            st.tok.copy_(keep[0]); st.pos.copy_(keep[1]); st.cu_k.copy_(keep[2]); st.step.copy_(keep[3])      # capture does not execute
+            setattr(st, gname, g)
+        getattr(st, gname).replay()
         if self.comm is not None:
             self.comm.sent_bytes += getattr(st, "graph_comm_bytes", 0)
 
@@ -1343,6 +1421,7 @@ class LeopardEngine:
     def decode_step(self, token_id: int, cache: KVCache) -> torch.Tensor:
         """Append one token: returns its logits [vocab] (fp32, a view of a static buffer) and advances the cache."""
         st = self._decode_state(cache)
+        st.sampling = False
         self._decode_seed(st, cache, token_id)
         self._decode_run(st, cache)
         cache.length += 1
@@ -1366,10 +1445,15 @@ class LeopardEngine:
             logits_last.index_fill_(0, self.suppress_tokens, float("-inf"))
         return int(logits_last.argmax())
 
-    def _greedy_loop(self, prompt_ids: List[int], first: int, cache: KVCache, max_new_tokens: int, eos) -> List[int]:
-        """EVAL:448-452 after the prefill: greedy tokens until eos / max_new_tokens; one captured decode step per token."""
+    def _greedy_loop(self, prompt_ids: List[int], first: int, cache: KVCache, max_new_tokens: int, eos,
+                     sampling: Optional[SamplingParams] = None) -> List[int]:
+        """EVAL:448-452 after the prefill: greedy tokens until eos / max_new_tokens; one captured decode step per token.  With ``sampling``
+        the step draws instead (the sampled graph; ``first`` was drawn at step 0)."""
         out, nxt = list(prompt_ids), int(first)
         st = self._decode_state(cache)
+        st.sampling = sampling is not None
+        if sampling is not None:
+            self._set_sampling(st, 0, sampling)
         self._decode_seed(st, cache, nxt)
         for step in range(max_new_tokens):
             out.append(nxt)
@@ -1382,15 +1466,16 @@ class LeopardEngine:
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, tiles: Optional[torch.Tensor], max_new_tokens: int = 128,
-                 eos_token_id: Sequence[int] = (128001, 128009)) -> torch.Tensor:
-        """Greedy generation (EVAL:448-452): returns LongTensor [1, S_in + T] on the input device."""
+                 eos_token_id: Sequence[int] = (128001, 128009), sampling: Optional[SamplingParams] = None) -> torch.Tensor:
+        """Greedy generation (EVAL:448-452), or sampled with ``sampling``: returns LongTensor [1, S_in + T] on the input device."""
         ids = input_ids.reshape(1, -1)
         n_img = int((ids == self.cfg.image_token_index).sum())
         S = ids.shape[1] + n_img * (self.cfg.tokens_per_tile - 1)
         cache = self._generation_cache((self.tp_padded_len(S) if self.tp_size > 1 else S) + max_new_tokens)
         res = self.prefill(ids, tiles, cache=cache)
-        out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], self.first_token(res.logits_last), cache, max_new_tokens,
-                                set(int(e) for e in eos_token_id))
+        first = self.first_token(res.logits_last) if sampling is None else self.sample_first(res.logits_last, [sampling])[0]
+        out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], first, cache, max_new_tokens,
+                                set(int(e) for e in eos_token_id), sampling)
         return torch.tensor([out], dtype=torch.long, device=input_ids.device)
 
     # ------------------------------------------------------------------------------------------------
@@ -1455,6 +1540,7 @@ class LeopardEngine:
         st.hist = torch.zeros(self.HIST, B, dtype=torch.int64, device=dev)
         st.hist_pos = torch.zeros(B, dtype=torch.int32, device=dev)
         st.graph = None
+        self._sampling_buffers(st, B)
         # bounded: a serving process that sees many batch sizes keeps the pools of the two most recent ones (each is B x capacity KV rows)
         while len(states) >= 2:
             states.pop(next(iter(states)))
@@ -1548,15 +1634,15 @@ class LeopardEngine:
             ops.gemm_skinny(self._skinny_head() if self.skinny_packed else W.lm_head, st.h, st.logits, 3)
         # greedy choice, history ring, stop rule (eos ids / token budget) and position advance of all B slots: ONE launch, device memory only —
         # a slot that stopped freezes (live = 0) and what it produces afterwards is ignored (lmi_decode_advance)
-        ops.decode_advance(st.logits, tc.vocab_size, st.tok, st.pos, k_len=st.k_len, live=st.live, budget=st.budget, eos=st.eos, hist=st.hist,
-                           hist_pos=st.hist_pos, suppress=self.suppress_tokens)
+        self._choose(st, st.logits, k_len=st.k_len, live=st.live, budget=st.budget, eos=st.eos, hist=st.hist, hist_pos=st.hist_pos)
 
     def _batch_decode_run(self, st):
         if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs:
             self._batch_decode_body(st)
             return
-        if st.graph is None:
-            names = ("tok", "pos", "k_len", "live", "budget", "hist", "hist_pos")
+        gname = "graph_s" if st.sampling else "graph"                      # greedy and sampled steps: one captured graph each
+        if getattr(st, gname) is None:
+            names = ("tok", "pos", "k_len", "live", "budget", "hist", "hist_pos", "step")
             keep = [getattr(st, n).clone() for n in names]
             side = torch.cuda.Stream(device=self.device)               # warm-up outside capture (function attributes, allocator)
             side.wait_stream(torch.cuda.current_stream(self.device))
@@ -1570,10 +1656,11 @@ class LeopardEngine:
                 self._batch_decode_body(st)
             for n, v in zip(names, keep):                              # capture does not execute
                 getattr(st, n).copy_(v)
-            st.graph = g
-        st.graph.replay()
+            setattr(st, gname, g)
+        getattr(st, gname).replay()
 
-    def _greedy_loop_batch(self, st, prompts: List[List[int]], first: List[int], seq_lens: List[int], max_new_tokens: int, eos) -> List[List[int]]:
+    def _greedy_loop_batch(self, st, prompts: List[List[int]], first: List[int], seq_lens: List[int], max_new_tokens: int, eos,
+                           sampling: Optional[Sequence[SamplingParams]] = None) -> List[List[int]]:
         """EVAL:448-452 for B sequences at once: every sequence follows exactly the batch-1 rule (emit, stop at eos / max_new_tokens);
         finished sequences keep riding along in the batch (their slots are private) and are ignored."""
         B = st.B
@@ -1584,6 +1671,9 @@ class LeopardEngine:
         st.pos.copy_(torch.tensor(seq_lens, dtype=torch.int32))
         st.k_len.copy_(torch.tensor([s + 1 for s in seq_lens], dtype=torch.int32))
         st.live.fill_(1); st.budget.fill_(1 << 30); st.eos.fill_(-1); st.hist_pos.zero_()      # the host applies the stop rule here
+        st.sampling = sampling is not None
+        for j, sp in enumerate(sampling or ()):
+            self._set_sampling(st, j, sp)
         for step in range(max_new_tokens):
             for j in range(B):
                 if not done[j]:
@@ -1609,7 +1699,8 @@ class LeopardEngine:
 
     @torch.no_grad()
     def generate_stream(self, samples: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8, max_new_tokens: int = 128,
-                        eos_token_id: Sequence[int] = (128001, 128009), stats: Optional[dict] = None) -> List[torch.Tensor]:
+                        eos_token_id: Sequence[int] = (128001, 128009), stats: Optional[dict] = None,
+                        sampling: Optional[SamplingParams] = None) -> List[torch.Tensor]:
         """CONTINUOUS batching (the reference loop EVAL:381-452 is one generate() per record): ``batch_size`` decode slots,
         ONE captured step per token for all of them, and a slot that finishes (eos / max_new_tokens) is handed to the next pending sample
         — prefill of the newcomer, its K / V rows copied into the slot of the pooled cache, five small device writes — without
@@ -1618,12 +1709,14 @@ class LeopardEngine:
         one blocking read per token; a slot that stopped inside the window idles until the window ends (its state is frozen).
         Returns the outputs in input order, each exactly what ``generate`` returns for that sample (same rule; the batched projections sum
         in a different order than the batch-1 GEMVs, so a token can differ only on a near tie of the top two logits).
-        ``stats`` (optional dict) receives steps / slot-steps / live slot-steps for occupancy accounting."""
+        ``stats`` (optional dict) receives steps / slot-steps / live slot-steps for occupancy accounting.
+        ``sampling``: sampled decoding; request i draws with ``sampling.for_request(i)``, so its tokens do not depend on ``batch_size``."""
         assert self.tp_size == 1, "batched generation is a single-rank feature (replicas scale it out)"
         B = max(1, min(int(batch_size), self.MAX_DECODE_BATCH, len(samples)))
         eos = [int(e) for e in eos_token_id]
+        req = (lambda i: None) if sampling is None else sampling.for_request
         if B == 1 or not self._batch_decode_supported() or len(eos) > self.MAX_EOS:
-            return [self.generate(ids, t() if callable(t) else t, max_new_tokens, eos) for ids, t in samples]
+            return [self.generate(ids, t() if callable(t) else t, max_new_tokens, eos, sampling=req(i)) for i, (ids, t) in enumerate(samples)]
         tpt = self.cfg.tokens_per_tile
         def merged_len(ids):
             return ids.shape[-1] + int((ids == self.cfg.image_token_index).sum()) * (tpt - 1)
@@ -1633,6 +1726,7 @@ class LeopardEngine:
         if eos:
             st.eos[:len(eos)].copy_(torch.tensor(eos, dtype=torch.int64))
         st.live.zero_(); st.budget.zero_(); st.pos.zero_(); st.k_len.fill_(1); st.tok.zero_(); st.hist_pos.zero_()
+        st.sampling = sampling is not None
         eos_set = set(eos)
         outs: List[Optional[List[int]]] = [None] * len(samples)
         slot_sample = [-1] * B                                       # which sample a slot runs (-1: free)
@@ -1654,7 +1748,7 @@ class LeopardEngine:
                     scratch = self._stream_cache = KVCache(self.cfg, (S + 1023) // 1024 * 1024, self.dtype, self.device)
                 scratch.length = 0
                 res = self.prefill(ids.reshape(1, -1), tiles, cache=scratch)
-                first = self.first_token(res.logits_last)
+                first = self.first_token(res.logits_last) if sampling is None else self.sample_first(res.logits_last, [req(i)])[0]
                 out = [int(t) for t in ids.reshape(-1).tolist()] + [first]
                 outs[i] = out
                 if first in eos_set or max_new_tokens <= 1:
@@ -1667,6 +1761,8 @@ class LeopardEngine:
                 st.k_len[j:j + 1].copy_(torch.tensor([S + 1], dtype=torch.int32, device=dev))
                 st.budget[j:j + 1].copy_(torch.tensor([max_new_tokens - 1], dtype=torch.int32, device=dev))
                 st.live[j:j + 1].fill_(1)
+                if sampling is not None:
+                    self._set_sampling(st, j, req(i))
                 slot_sample[j], h_budget[j] = i, max_new_tokens - 1
                 return True
             return False
@@ -1701,7 +1797,8 @@ class LeopardEngine:
 
     @torch.no_grad()
     def generate_batch(self, samples: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], max_new_tokens: int = 128,
-                       eos_token_id: Sequence[int] = (128001, 128009)) -> List[torch.Tensor]:
+                       eos_token_id: Sequence[int] = (128001, 128009), sampling: Optional[SamplingParams] = None,
+                       _first_request: int = 0) -> List[torch.Tensor]:
         """Several samples per call (batching with per-sample cu_seqlens instead of one sample per generate()):
         ONE packed prefill — all ViT inputs through the tower together, all merged sequences in one varlen causal pass that also
         writes every sample's K/V into a packed cache — then each sample's K/V rows move to its slot of the pooled decode cache (a
@@ -1709,16 +1806,18 @@ class LeopardEngine:
         (``_batch_decode_body``: the weight stream of a step is shared by the batch).  Same RULE as per-sample ``generate`` and numerically
         equivalent, not bit-identical: the first new token comes from the same prefill, the continuation's projections are MFMA tiles with folded
         norms instead of the batch-1 FMA chains, so a greedy choice can differ where the top two logits are within the 16-bit noise (the GPU
-        tests assert equality and, where it fails, exactly such a near tie)."""
+        tests assert equality and, where it fails, exactly such a near tie).
+        ``sampling``: sampled decoding, request i with ``sampling.for_request(i)`` (as generate_stream)."""
         assert self.tp_size == 1, "batched generation is a single-rank feature (replicas scale it out)"
         if len(samples) > self.MAX_DECODE_BATCH:
             outs = []
             for i in range(0, len(samples), self.MAX_DECODE_BATCH):
-                outs += self.generate_batch(samples[i:i + self.MAX_DECODE_BATCH], max_new_tokens, eos_token_id)
+                outs += self.generate_batch(samples[i:i + self.MAX_DECODE_BATCH], max_new_tokens, eos_token_id, sampling, _first_request + i)
             return outs
+        req = (lambda i: None) if sampling is None else (lambda i: sampling.for_request(_first_request + i))
         if len(samples) == 1:
             ids, t = samples[0]
-            return [self.generate(ids, t, max_new_tokens, eos_token_id)]
+            return [self.generate(ids, t, max_new_tokens, eos_token_id, sampling=req(0))]
         tiles = [t for _, t in samples if t is not None and t.shape[0] > 0]
         visual = None
         if tiles:
@@ -1736,19 +1835,22 @@ class LeopardEngine:
             seq_lens.append(x.shape[0])
         packed = KVCache(self.cfg, sum(seq_lens), self.dtype, self.device)
         last, _ = self.llm_prefill(torch.cat(xs, dim=0), seq_lens, cache=packed)
-        first = [self.first_token(last[j]) for j in range(last.shape[0])]
+        if sampling is None:
+            first = [self.first_token(last[j]) for j in range(last.shape[0])]
+        else:
+            first = self.sample_first(last, [req(j) for j in range(last.shape[0])])
         eos = set(int(e) for e in eos_token_id)
         if not self._batch_decode_supported():
             # shapes the skinny-M kernels do not cover (toy configurations): the samples continue one after another on the engine's ONE
             # generation cache and its captured batch-1 step
             outs, off = [], 0
-            for (ids, _), S, nxt in zip(samples, seq_lens, first):
+            for j, ((ids, _), S, nxt) in enumerate(zip(samples, seq_lens, first)):
                 cache = self._generation_cache(S + max_new_tokens)
                 for i in range(len(cache.k)):
                     self.ops.kv_append(packed.k[i][off:off + S], packed.v[i][off:off + S], cache.k[i], cache.v[i], 0)
                 cache.length = S
                 off += S
-                out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], nxt, cache, max_new_tokens, eos)
+                out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], nxt, cache, max_new_tokens, eos, req(j))
                 outs.append(torch.tensor([out], dtype=torch.long, device=ids.device))
             return outs
         st = self._batch_state(len(samples), max(seq_lens) + max_new_tokens)
@@ -1759,5 +1861,6 @@ class LeopardEngine:
             off += S
         del packed
         prompts = [[int(t) for t in ids.reshape(-1).tolist()] for ids, _ in samples]
-        outs = self._greedy_loop_batch(st, prompts, first, seq_lens, max_new_tokens, eos)
+        outs = self._greedy_loop_batch(st, prompts, first, seq_lens, max_new_tokens, eos,
+                                       None if sampling is None else [req(j) for j in range(len(samples))])
         return [torch.tensor([o], dtype=torch.long, device=ids.device) for o, (ids, _) in zip(outs, samples)]

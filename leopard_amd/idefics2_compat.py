@@ -31,6 +31,7 @@ from .config import Idefics2Config, PerceiverConfig, TextConfig, VisionConfig
 from .engine import KVCache
 from .idefics2 import Idefics2Engine, Idefics2Weights, preprocess_image_u8
 from .ops import Ops
+from . import sampling
 
 IMAGE_TOKEN = "<image>"
 FAKE_TOKEN = "<fake_token_around_image>"
@@ -160,6 +161,8 @@ class Idefics2ForConditionalGeneration:
         self.precision = "fast"
         self._engine: Optional[Idefics2Engine] = None
         self.device = torch.device("cpu")
+        self.generation_defaults: dict = {}              # do_sample / temperature / top_k / top_p of generation_config.json
+        self.last_decoding = "greedy"
 
     @classmethod
     def from_pretrained(cls, path: str, torch_dtype=torch.float16, ops: Optional[Ops] = None, patch_validity: str = "any",
@@ -179,6 +182,7 @@ class Idefics2ForConditionalGeneration:
         dtype = torch_dtype if torch_dtype in (torch.float16, torch.bfloat16) else torch.float16
         m = cls(cfg, lambda dev, dt: CheckpointSource(path, dev, dt), dtype, ops, eos, bad)
         m.patch_validity = patch_validity
+        m.generation_defaults = sampling.read_generation_config(path)
         from .compat import resolve_precision
         m.precision = resolve_precision(torch_dtype, dtype, precision)
         return m
@@ -245,7 +249,12 @@ class Idefics2ForConditionalGeneration:
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, pixel_values=None, pixel_attention_mask=None, max_new_tokens: int = 128,
-                 eos_token_id=None, **unused) -> torch.Tensor:
+                 eos_token_id=None, do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None,
+                 **unused) -> torch.Tensor:
+        """Greedy, or sampled with ``do_sample=True`` (HF semantics, generation_config.json defaults: leopard_amd.sampling)."""
+        sampling.warn_unsupported("generate", unused)
+        sp = sampling.resolve(self.generation_defaults, do_sample, temperature, top_k, top_p, seed)
+        self.last_decoding = sampling.describe(sp)
         if input_ids.shape[0] != 1:
             raise NotImplementedError("batch 1 per call, as in the reference script (IDEF:88-97)")
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
@@ -257,6 +266,6 @@ class Idefics2ForConditionalGeneration:
         ids = input_ids.reshape(1, -1)
         cache = eng._generation_cache(ids.shape[1] + max_new_tokens)           # one cache + captured decode graph per engine
         res = eng.prefill(ids.to(self.device), images, cache=cache)
-        out = eng._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], eng.first_token(res.logits_last), cache, max_new_tokens,
-                               set(int(e) for e in eos))
+        first = eng.first_token(res.logits_last) if sp is None else eng.sample_first(res.logits_last, [sp])[0]
+        out = eng._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], first, cache, max_new_tokens, set(int(e) for e in eos), sp)
         return torch.tensor([out], dtype=torch.long, device=input_ids.device)

@@ -310,6 +310,19 @@ class Ops:
                                                 _ptr(tok), _ptr(pos), _ptr(k_len), _ptr(live), _ptr(budget), _ptr(eos), 0 if eos is None else eos.numel(),
                                                 _ptr(hist), _ptr(hist_pos), 0 if hist is None else hist.shape[0], self._stream(logits)))
 
+    def decode_sample(self, logits, vocab, temperature, top_k, top_p, seed, step, tok, pos, k_len=None, live=None, budget=None, eos=None,
+                      hist=None, hist_pos=None, suppress=None):
+        """lmi_decode_sample: the sampled form of decode_advance (temperature / top-k / top-p, Philox keyed by ``seed`` at ``step``).
+        Per-row parameters are device tensors of length B: temperature fp32, top_k int32, top_p fp32, seed int64 (read as uint64), step int32."""
+        B = logits.shape[0]
+        for t, dt in ((temperature, torch.float32), (top_k, torch.int32), (top_p, torch.float32), (seed, torch.int64), (step, torch.int32)):
+            if t.dtype != dt or t.numel() < B:
+                raise TypeError(f"leopard_amd: decode_sample parameter must be {dt} with >= {B} entries, got {t.dtype} [{t.numel()}]")
+        self._check(self.lib.lmi_decode_sample(_ptr(logits), B, int(vocab), logits.stride(0), _ptr(suppress), 0 if suppress is None else suppress.numel(),
+                                               _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(seed), _ptr(step),
+                                               _ptr(tok), _ptr(pos), _ptr(k_len), _ptr(live), _ptr(budget), _ptr(eos), 0 if eos is None else eos.numel(),
+                                               _ptr(hist), _ptr(hist_pos), 0 if hist is None else hist.shape[0], self._stream(logits)))
+
     def decode_workspace_elems(self, q_rows, n_heads, head_dim, max_seqlen_k) -> int:
         n = int(self.lib.lmi_attn_decode_workspace_bytes(q_rows, n_heads, head_dim, max_seqlen_k))
         if n < 0:

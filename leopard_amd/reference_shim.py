@@ -76,7 +76,8 @@ _PRECISION_TEXT = {"fast": "fast (one rounding per MFMA-operand hand-over)",
                    "split": "split operands (hi + lo 16-bit pairs, GEMMs at 2 K)"}
 
 
-def _record_run_info(model_class: str, checkpoint: str, requested, compute, precision: str = "fast", warn: bool = True) -> None:
+def _record_run_info(model_class: str, checkpoint: str, requested, compute, precision: str = "fast", warn: bool = True,
+                     decoding: str = "greedy") -> None:
     """Side file of the result rows: what arithmetic the script's ``torch_dtype`` request was actually served with.  Written where the
     script writes its result shards — the checkpoint directory (EVAL:496-497) — or ``LEOPARD_AMD_RUN_INFO_DIR``; a location that cannot be
     written falls back to the working directory, then to the warning alone."""
@@ -89,7 +90,7 @@ def _record_run_info(model_class: str, checkpoint: str, requested, compute, prec
                       UserWarning, stacklevel=3)
     info = {"model_class": model_class, "checkpoint": str(checkpoint), "requested_torch_dtype": req, "compute_dtype": cmp_,
             "accumulate_dtype": "float32", "residual_stream_dtype": "float32",
-            "precision_mode": _PRECISION_TEXT.get(precision, precision), "library": os.environ.get("LEOPARD_AMD_LIB") or "libleopard_amd.so",
+            "precision_mode": _PRECISION_TEXT.get(precision, precision), "decoding": decoding, "library": os.environ.get("LEOPARD_AMD_LIB") or "libleopard_amd.so",
             "fallback_scorers": sorted(_FALLBACK_SCORERS)}
     for d in (os.environ.get("LEOPARD_AMD_RUN_INFO_DIR"), str(checkpoint) if os.path.isdir(str(checkpoint)) else None, "."):
         if not d:
@@ -149,6 +150,8 @@ def _llava_class():
                 m = cls(cfg)
             finally:
                 cls._pending = None
+            from .sampling import read_generation_config
+            m.generation_defaults = read_generation_config(path)      # HF: generate() takes do_sample / temperature / top_k / top_p from it
             m._run_info = (path, torch_dtype, compute_dtype, recorded)
             return m
 
@@ -156,12 +159,18 @@ def _llava_class():
             m = super().to(_device(device))
             info = getattr(self, "_run_info", None)
             if info is not None and self.precision != info[3]:      # the engine fell back (a shape lo4 does not cover): the side file says what RAN
-                _record_run_info("LlavaForConditionalGeneration", info[0], info[1], info[2], self.precision, warn=False)
+                _record_run_info("LlavaForConditionalGeneration", info[0], info[1], info[2], self.precision, warn=False,
+                                 decoding=getattr(self, "_run_decoding", "greedy"))
                 self._run_info = info[:3] + (self.precision,)
             return m
 
         def generate(self, *args, max_new_tokens=128, **kw):
-            return super().generate(*args, max_new_tokens=_cap_tokens(max_new_tokens), **kw)
+            out = super().generate(*args, max_new_tokens=_cap_tokens(max_new_tokens), **kw)
+            info = getattr(self, "_run_info", None)
+            if info is not None and self.last_decoding != getattr(self, "_run_decoding", "greedy"):    # the side file says which rule RAN
+                self._run_decoding = self.last_decoding
+                _record_run_info("LlavaForConditionalGeneration", info[0], info[1], info[2], info[3], warn=False, decoding=self.last_decoding)
+            return out
 
         # the reference's subclass overrides forward() with EVAL:201-361, which needs HF sub-modules; calls go to the engine
         def __call__(self, *args, **kw):
@@ -180,13 +189,19 @@ def _idefics2_classes():
             req = kw.get("torch_dtype", torch.float16)
             m = super().from_pretrained(path, **kw)
             _record_run_info("AutoModelForVision2Seq", path, req, m.compute_dtype, getattr(m, "precision", "fast"))
+            m._run_info = (path, req, m.compute_dtype, getattr(m, "precision", "fast"))
             return m
 
         def to(self, device):
             return super().to(_device(device))
 
         def generate(self, *args, max_new_tokens=128, **kw):
-            return super().generate(*args, max_new_tokens=_cap_tokens(max_new_tokens), **kw)
+            out = super().generate(*args, max_new_tokens=_cap_tokens(max_new_tokens), **kw)
+            info = getattr(self, "_run_info", None)
+            if info is not None and self.last_decoding != getattr(self, "_run_decoding", "greedy"):    # the side file says which rule RAN
+                self._run_decoding = self.last_decoding
+                _record_run_info("AutoModelForVision2Seq", *info, warn=False, decoding=self.last_decoding)
+            return out
     return IC.Idefics2Processor, AutoModelForVision2Seq
 
 

@@ -1,0 +1,64 @@
+"""HF-style decoding arguments of the generate() surfaces (compat, idefics2_compat, reference_shim) -> LeopardEngine's SamplingParams.
+
+HF semantics: ``do_sample`` False or absent = greedy (bit-identical to the greedy path); with ``do_sample=True`` an argument left unset
+takes the checkpoint's generation_config.json value, else HF's default (temperature 1.0, top_k 50, top_p 1.0); ``temperature <= 0``
+with sampling raises ValueError.  The per-call seed comes from torch's default CPU generator (``torch.manual_seed(s)`` makes a run
+reproducible) unless ``seed=`` is passed.  Options this library does not implement (beam search, penalties, min-p, ...) produce one
+warning naming them instead of being ignored silently."""
+from __future__ import annotations
+
+import json
+import os
+import warnings
+from typing import Optional
+
+import torch
+
+from .engine import SamplingParams
+
+HF_DEFAULTS = {"temperature": 1.0, "top_k": 50, "top_p": 1.0}
+SAMPLING_KEYS = ("do_sample", "temperature", "top_k", "top_p")
+# generate() options that change the decoding rule and are not implemented, with the value that means "off"
+UNSUPPORTED = {"num_beams": 1, "num_beam_groups": 1, "penalty_alpha": None, "repetition_penalty": 1.0, "encoder_repetition_penalty": 1.0,
+               "length_penalty": 1.0, "no_repeat_ngram_size": 0, "min_p": None, "typical_p": 1.0, "epsilon_cutoff": 0.0,
+               "eta_cutoff": 0.0, "num_return_sequences": 1, "diversity_penalty": 0.0, "sequence_bias": None, "guidance_scale": None,
+               "low_memory": None, "prompt_lookup_num_tokens": None, "assistant_model": None, "logits_processor": None,
+               "min_new_tokens": None, "min_length": None, "renormalize_logits": False, "force_words_ids": None,
+               "constraints": None}
+
+
+def read_generation_config(path: str) -> dict:
+    """The sampling keys of ``<path>/generation_config.json`` (empty when the file or the keys are absent)."""
+    gpath = os.path.join(str(path), "generation_config.json")
+    if not os.path.exists(gpath):
+        return {}
+    with open(gpath) as f:
+        g = json.load(f)
+    return {k: g[k] for k in SAMPLING_KEYS if g.get(k) is not None}
+
+
+def warn_unsupported(where: str, kwargs: dict) -> None:
+    bad = sorted(k for k, off in UNSUPPORTED.items() if k in kwargs and kwargs[k] is not None and kwargs[k] != off)
+    if bad:
+        warnings.warn(f"{where}: {', '.join(bad)} {'is' if len(bad) == 1 else 'are'} not supported by leopard_amd and ignored "
+                      "(decoding is greedy or temperature / top-k / top-p sampling)", UserWarning, stacklevel=3)
+
+
+def resolve(defaults: Optional[dict] = None, do_sample=None, temperature=None, top_k=None, top_p=None,
+            seed: Optional[int] = None) -> Optional[SamplingParams]:
+    """None = greedy; otherwise the SamplingParams of this call (call arguments over ``defaults`` over HF's defaults)."""
+    d = defaults or {}
+    if not bool(do_sample if do_sample is not None else d.get("do_sample", False)):
+        return None
+    t = temperature if temperature is not None else d.get("temperature", HF_DEFAULTS["temperature"])
+    k = top_k if top_k is not None else d.get("top_k", HF_DEFAULTS["top_k"])
+    p = top_p if top_p is not None else d.get("top_p", HF_DEFAULTS["top_p"])
+    if not float(t) > 0:
+        raise ValueError(f"`temperature` (={t}) has to be a strictly positive float when sampling")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())        # torch's default CPU generator: torch.manual_seed(s) reproduces the run
+    return SamplingParams(float(t), int(k), float(p), int(seed))
+
+
+def describe(params: Optional[SamplingParams]) -> str:
+    return "greedy" if params is None else params.describe()
