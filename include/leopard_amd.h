@@ -472,6 +472,21 @@ int lmi_gemv_rmsnorm_rope(const void* Wqkv_rope, const float* x, const float* no
 int lmi_lm_head_last(const void* W, const float* x, const int64_t* rows, const float* norm_weight, float eps, float* out, int n_rows,
                      int N, int K, int ldw, int ldx, int ldo, int dtype, void* stream);
 
+/* Final RMSNorm of a GATHERED set of rows (the head of scoring, LeopardEngine.score): out[r] = T(w * (x[rows[r]] * rstd)) with the element
+ * arithmetic of lmi_rmsnorm — the bits lmi_rmsnorm writes for that row in a pass over the whole stream.  x fp32 [., ldx], rows int64 [n_rows]
+ * on device, out T [n_rows, ldo]; D % 8 == 0, D <= 4096; dtype LMI_F16 | LMI_BF16. */
+int lmi_rmsnorm_rows(const float* x, const int64_t* rows, const float* w, void* out, int n_rows, int D, int ldx, int ldo, float eps, int dtype,
+                     void* stream);
+
+/* Token log-likelihoods (forward(labels=) / scoring; the log-softmax + gather of nn.CrossEntropyLoss, EVAL:333-348): for each of n_rows rows
+ * of fp32 logits [., ld] (row rows[r], int64 on device; null = row r) with the vocabulary in columns [0, vocab):
+ *     lse[r] = log sum_{i < vocab} exp(logit_i),  logprob[r] = logit[targets[r]] - lse[r],  argmax[r] = lowest index of the largest logit.
+ * Columns >= vocab (the head's padding) are never read.  targets int64 [n_rows] on device; a target outside [0, vocab) gives logprob NaN (the
+ * launch does not read it back: callers validate targets on the host).  ld >= vocab, ld % 4 == 0, logits 16-byte aligned.  One pass over
+ * each row, fixed reduction order, no atomics (run-to-run bit-identical), no allocation, graph-capturable.  leopard_amd/csrc/logprob.h. */
+int lmi_token_logprobs(const float* logits, const int64_t* rows, const int64_t* targets, int n_rows, int vocab, int ld, float* logprob, float* lse,
+                       int64_t* argmax, void* stream);
+
 /* ---- multi-GPU: RCCL collectives over xGMI (SURVEY.md 8(b) "lmi_allgather / lmi_allreduce wrappers over RCCL communicators
  * ... created by lmi_comm_init(rank, nranks, unique_id) and freed by lmi_comm_destroy", 8(e)).  The reference's evaluation is one
  * process per GPU with no collective (run_eval_llava_siglip_multiimg.sh:9-11); its training side states the exchange pattern

@@ -126,8 +126,8 @@ class LeopardForConditionalGeneration:
     def forward(self, input_ids=None, pixel_values=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, vision_feature_layer=None, vision_feature_select_strategy=None, labels=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None):
-        if inputs_embeds is not None or labels is not None or output_attentions or output_hidden_states:
-            raise NotImplementedError("inference surface only: input_ids (+ pixel_values), no labels / attentions")
+        if inputs_embeds is not None or output_attentions or output_hidden_states:
+            raise NotImplementedError("input_ids (+ pixel_values, labels) only: no inputs_embeds / attentions / hidden states")
         if input_ids.shape[0] != 1:
             raise NotImplementedError("batch 1 per call, as in the reference harness (EVAL:381-452)")
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
@@ -136,13 +136,32 @@ class LeopardForConditionalGeneration:
         if past_key_values is not None and input_ids.shape[1] == 1:          # decode branch, EVAL:291-320
             logits = eng.decode_step(int(input_ids[0, 0]), past_key_values)
             return LlavaCausalLMOutputWithPast(logits=logits.view(1, 1, -1), past_key_values=past_key_values)
+        if labels is not None:
+            if past_key_values is not None:
+                raise NotImplementedError("labels score a whole prompt: no past_key_values")
+            rows, targets, _ = eng.score_targets(input_ids, labels)          # ValueError on bad labels, before any launch
         tiles = self._as_tiles(pixel_values)
         S = input_ids.shape[1] + int((input_ids == self.config.image_token_index).sum()) * (self.config.tokens_per_tile - 1)
         cache = KVCache(self.config, S + 256, self.compute_dtype, self.device) if use_cache else None
         res = eng.prefill(input_ids.to(self.device), tiles, cache=cache, all_logits=True)
-        return LlavaCausalLMOutputWithPast(logits=res.logits_all.unsqueeze(0), past_key_values=cache)
+        loss = None
+        if labels is not None:
+            # EVAL:333-348: the mean cross-entropy of the shifted labels over their non-ignored targets (nan when there are none), from the
+            # logits just computed (lmi_token_logprobs on the scored rows: no second head pass)
+            lp, _ = eng.logits_logprobs(res.logits_all, rows, targets)
+            loss = (-lp.to(torch.float64).mean()).to(torch.float32) if len(rows) else torch.full((), float("nan"), device=self.device)
+        return LlavaCausalLMOutputWithPast(loss=loss, logits=res.logits_all.unsqueeze(0), past_key_values=cache)
 
     __call__ = forward
+
+    @torch.no_grad()
+    def loglikelihood(self, requests: Sequence[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8
+                      ) -> List[Tuple[float, bool]]:
+        """The ``loglikelihood`` contract of VLM evaluation harnesses: [(context_ids [1, S_c], continuation_ids [1, S_t], pixel_values)] ->
+        [(sum of log p(continuation | images + context), is_greedy)].  The continuation is appended to the context, the context labelled -100,
+        and the requests are scored ``batch_size`` at a time in one packed prefill each (LeopardEngine.score_batch); is_greedy = every
+        continuation token is its row's argmax."""
+        return score_loglikelihood(self.engine, [(c, t, self._as_tiles(p)) for c, t, p in requests], batch_size, self.device)
 
     # ---- EVAL:448-452 ------------------------------------------------------------------------------------------
     def _sampling(self, where: str, unused: dict, do_sample, temperature, top_k, top_p, seed):
@@ -191,6 +210,23 @@ class LeopardForConditionalGeneration:
         samples = [(ids.to(self.device), (lambda f=pix: self._as_tiles(f())) if callable(pix) else self._as_tiles(pix)) for ids, pix in requests]
         return self.engine.generate_stream(samples, batch_size=batch_size, max_new_tokens=max_new_tokens, eos_token_id=eos, stats=stats,
                                            sampling=sp)
+
+
+def score_loglikelihood(engine: LeopardEngine, requests, batch_size: int, device) -> List[Tuple[float, bool]]:
+    """loglikelihood() of the model surfaces: requests [(context_ids, continuation_ids, tiles / images)] through engine.score_batch."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    packed = []
+    for ctx, cont, vis in requests:
+        ctx, cont = torch.as_tensor(ctx).reshape(1, -1).to(torch.int64), torch.as_tensor(cont).reshape(1, -1).to(torch.int64)
+        ids = torch.cat([ctx.cpu(), cont.cpu()], dim=1)
+        labels = torch.cat([torch.full_like(ctx.cpu(), LeopardEngine.IGNORE_INDEX), cont.cpu()], dim=1)
+        packed.append((ids.to(device), vis, labels))
+    out = []
+    for i in range(0, len(packed), batch_size):
+        for r in engine.score_batch(packed[i:i + batch_size]):
+            out.append((float(r.token_logprobs.to(torch.float64).sum()), bool((r.argmax == r.target_ids).all())))
+    return out
 
 
 def from_pretrained(path: str, torch_dtype=torch.float32, **kw) -> LeopardForConditionalGeneration:

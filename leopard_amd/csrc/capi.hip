@@ -17,6 +17,7 @@
 #include "lowbit.h"
 #include "skinny.h"
 #include "sample.h"
+#include "logprob.h"
 
 using namespace lmi;
 
@@ -1539,6 +1540,41 @@ int lmi_lm_head_last(const void* W, const float* x, const int64_t* rows, const f
     else
         return fail(LMI_EINVAL, "lmi_lm_head_last: dtype must be LMI_F16 or LMI_BF16");
     return check_launch("lmi_lm_head_last");
+}
+
+int lmi_rmsnorm_rows(const float* x, const int64_t* rows, const float* w, void* out, int n_rows, int D, int ldx, int ldo, float eps, int dtype,
+                     void* stream) {
+    if (!x || !rows || !w || !out || n_rows < 0 || D <= 0 || (D & 7) || D > 4096 || (ldx & 3) || (ldo & 7) || !aligned16(x) || !aligned16(w) ||
+        !aligned16(out))
+        return fail(LMI_EINVAL, "lmi_rmsnorm_rows: bad argument (n_rows=%d D=%d ldx=%d ldo=%d; D%%8==0, D<=4096)", n_rows, D, ldx, ldo);
+    if (n_rows == 0) return LMI_OK;
+    // always one wave per row (norm_kernel, lmi_rmsnorm's path for M > 32): the gathered rows get the bits lmi_rmsnorm gives them in a pass
+    // over the whole stream, however few they are
+    const int grid = (n_rows + 3) / 4;
+#define LMI_NORM_ROWS(T_)                                                                                                                   \
+    do {                                                                                                                                    \
+        if (D <= 1536) LMI_LAUNCH((norm_kernel<T_, true, 3, false, true>), dim3(grid), dim3(256), 0, stream, x, w, nullptr, (T_*)out, n_rows, D, \
+                                  ldx, ldo, eps, 1.0f, NormLo4(), rows);                                                                     \
+        else LMI_LAUNCH((norm_kernel<T_, true, 8, false, true>), dim3(grid), dim3(256), 0, stream, x, w, nullptr, (T_*)out, n_rows, D, ldx,    \
+                        ldo, eps, 1.0f, NormLo4(), rows);                                                                                    \
+    } while (0)
+    if (dtype == LMI_F16) LMI_NORM_ROWS(f16_t);
+    else if (dtype == LMI_BF16) LMI_NORM_ROWS(bf16_t);
+    else return fail(LMI_EINVAL, "lmi_rmsnorm_rows: dtype must be LMI_F16 or LMI_BF16");
+#undef LMI_NORM_ROWS
+    return check_launch("lmi_rmsnorm_rows");
+}
+
+int lmi_token_logprobs(const float* logits, const int64_t* rows, const int64_t* targets, int n_rows, int vocab, int ld, float* logprob, float* lse,
+                       int64_t* argmax, void* stream) {
+    if (!logits || !targets || !logprob || !lse || !argmax || n_rows < 0 || vocab <= 0 || ld < vocab || (ld & 3) || !aligned16(logits))
+        return fail(LMI_EINVAL, "lmi_token_logprobs: bad argument (n_rows=%d vocab=%d ld=%d; ld >= vocab, ld %% 4 == 0, 16-byte aligned logits)",
+                    n_rows, vocab, ld);
+    if (n_rows == 0) return LMI_OK;
+    TokenLogprobArgs a;
+    a.logits = logits; a.rows = rows; a.targets = targets; a.vocab = vocab; a.ld = ld; a.logprob = logprob; a.lse = lse; a.argmax = argmax;
+    LMI_LAUNCH(token_logprobs_kernel, dim3(n_rows), dim3(kLogprobThreads), 0, stream, a);
+    return check_launch("lmi_token_logprobs");
 }
 
 int lmi_gemv_rmsnorm(const void* W, const float* x, const float* norm_weight, float eps, void* out, int N, int K, int ldw,

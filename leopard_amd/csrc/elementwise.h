@@ -122,14 +122,16 @@ struct NormLo4 {
     int ld4, lds, K4;
     const uint8_t* row_sel;      // [M] or null: rows whose image is wanted (gemm.h GemmArgs::row_sel); the others get T(y) only
 };
-template <typename T, bool RMS, int MAXV, bool LO4 = false>     // MAXV = max 8-element chunks per lane (D <= MAXV*512)
+// GATHER (lmi_rmsnorm_rows): output row r normalises input row x_rows[r] — the same element arithmetic on a gathered set of rows.
+template <typename T, bool RMS, int MAXV, bool LO4 = false, bool GATHER = false>     // MAXV = max 8-element chunks per lane (D <= MAXV*512)
 __global__ void __launch_bounds__(256) norm_kernel(const float* x, const float* w, const float* b, T* out,
-                                                   int M, int D, int ldx, int ldo, float eps, float out_scale, NormLo4 lo = NormLo4()) {
+                                                   int M, int D, int ldx, int ldo, float eps, float out_scale, NormLo4 lo = NormLo4(),
+                                                   const int64_t* x_rows = nullptr) {
     typedef typename vec_of<T>::x8 T8;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
-    const float* xr = x + (long)row * ldx;
+    const float* xr = x + (GATHER ? (long)x_rows[row] : (long)row) * ldx;
     const int nvec = D >> 3;                         // 8-element chunks in the row (D % 8 == 0): 32 B in, 16 B out per lane
     f32x4 v[MAXV][2];
     float s = 0.f;

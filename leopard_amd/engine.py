@@ -17,6 +17,8 @@ between kernels are the 16-bit compute type; weights are converted once at load 
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import math
 import os
 from dataclasses import dataclass
@@ -82,6 +84,17 @@ class PrefillResult:
     parts: Optional[Dict[str, torch.Tensor]] = None
 
 
+@dataclass
+class ScoreResult:
+    """LeopardEngine.score: the labelled tokens of one request under the model (EVAL:333-348 semantics over merged rows)."""
+    loss: torch.Tensor                           # fp32 0-dim (device): mean of -token_logprobs; nan when nothing is labelled
+    token_logprobs: torch.Tensor                 # fp32 [n]: log p(target | rows <= row)
+    argmax: torch.Tensor                         # int64 [n]: the most likely token of the row (lowest index on ties)
+    target_ids: torch.Tensor                     # int64 [n]
+    rows: torch.Tensor                           # int64 [n]: merged rows that predict the targets (row s predicts merged label s + 1)
+    seq_len: int
+
+
 class KVCache:
     def __init__(self, cfg: LeopardConfig, capacity: int, dtype, device, tp_size: int = 1):
         tc = cfg.text_config
@@ -115,6 +128,20 @@ class SamplingParams:
 
     def describe(self) -> str:
         return f"sample(temperature={self.temperature:g}, top_k={int(self.top_k)}, top_p={self.top_p:g})"
+
+
+@contextlib.contextmanager
+def _capture_safe():
+    """Hold off Python's cyclic garbage collector while a HIP graph is captured.  A collection that starts inside the capture runs the
+    finalizers of whatever dead cycle it finds there — an engine left by an earlier caller, with its own captured graphs and events — and
+    releasing those is not allowed on a capturing stream: the process aborts.  The garbage is collected after the capture instead."""
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 def _signed64(v: int) -> int:
@@ -187,6 +214,9 @@ class LeopardEngine:
         self.lo4_rows = env_rows if env_rows in ("auto", "all") else int(env_rows)
         self.decode_precision = os.environ.get("LMI_DECODE_PRECISION", "1") == "1"   # lo4 / split also cover the decode steps (decode_hl); 0 = fast decode (A/B)
         self._lo4_sel_cache: Dict[tuple, tuple] = {}
+        self._score_sel_cache: Dict[tuple, tuple] = {}   # lo4 selections that include scored rows (_lo4_selection with extra rows)
+        self.last_lo4_ranges = None    # [n, 2] int32 [begin, end) packed rows the last lo4 LLM pass corrected (None: no lo4 pass ran)
+        self.score_chunk_rows = 1024   # score(): rows per head GEMM into the reusable fp32 chunk (525 MB at V = 128 256)
         self.skinny_fold_norm = True   # batched decode: RMSNorms folded into the projections (lmi_gemm_skinny_ex producer / consumer); False: norm launches
         self.skinny_packed = True      # batched decode over nn.Linear-layout weights (TP, pack_llm_weights=False): stream a packed second copy
         self.fp8_fused = True          # fp8 schedule: attention writes the fp8 o_proj operand, q|k|v GEMM does RoPE + KV append (False: separate launches)
@@ -621,12 +651,15 @@ class LeopardEngine:
             return seq_len if seq_len <= self.LO4_FULL_BELOW else min(self.LO4_TAIL_ROWS, seq_len)
         return max(1, min(int(r), seq_len))
 
-    def _lo4_selection(self, seq_lens: Sequence[int]):
+    def _lo4_selection(self, seq_lens: Sequence[int], extra_rows: Optional[np.ndarray] = None):
         """(row_sel uint8 [S], unit_sel uint8 [ceil(S / 64)]) device tensors + the host [n, 2] int32 array of the selected row ranges (the
-        tile-order hint of lmi_lo4.sel_ranges) for the packed rows of ``seq_lens``, or None when every row is selected."""
+        tile-order hint of lmi_lo4.sel_ranges) for the packed rows of ``seq_lens``, or None when every row is selected.  ``extra_rows``:
+        packed rows whose logits are read besides the tails (the scored rows of score / score_batch): selected as well."""
         tails = [self.lo4_tail_rows(int(l)) for l in seq_lens]
         if all(t == int(l) for t, l in zip(tails, seq_lens)):
             return None
+        if extra_rows is not None and len(extra_rows):
+            return self._lo4_selection_extra(seq_lens, tails, np.asarray(extra_rows, dtype=np.int64))
         key = (tuple(int(l) for l in seq_lens), tuple(tails))
         hit = self._lo4_sel_cache.get(key)
         if hit is None:
@@ -647,6 +680,31 @@ class LeopardEngine:
                 self._lo4_sel_cache.pop(next(iter(self._lo4_sel_cache)))
             hit = self._lo4_sel_cache[key] = (self._pinned_to_device(torch.from_numpy(row)), self._pinned_to_device(torch.from_numpy(unit)),
                                               np.ascontiguousarray(np.array(ranges, dtype=np.int32).reshape(-1, 2)))
+        return hit
+
+    def _lo4_selection_extra(self, seq_lens, tails, extra: np.ndarray):
+        """_lo4_selection of the tails united with ``extra``.  The tables are built with a synchronous copy (ready before any stream reads
+        them) and cached per launch stream, under a key that holds the extra rows themselves."""
+        sid = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+        key = (sid, tuple(int(l) for l in seq_lens), tuple(tails), extra.tobytes())
+        hit = self._score_sel_cache.get(key)
+        if hit is None:
+            S = int(sum(key[1]))
+            row = np.zeros(S, dtype=np.uint8)
+            end = 0
+            for l, t in zip(key[1], tails):
+                end += l
+                row[end - t:end] = 1
+            row[extra] = 1
+            if row.all():
+                return None
+            unit = np.zeros((S + 63) // 64 * 64, dtype=np.uint8)
+            unit[:S] = row
+            ranges = np.flatnonzero(np.diff(np.concatenate([[0], row.astype(np.int8), [0]]))).reshape(-1, 2)
+            if len(self._score_sel_cache) >= 16:
+                self._score_sel_cache.pop(next(iter(self._score_sel_cache)))
+            hit = self._score_sel_cache[key] = (torch.from_numpy(row).to(self.device), torch.from_numpy(unit.reshape(-1, 64).max(axis=1)).to(self.device),
+                                                np.ascontiguousarray(ranges.astype(np.int32)))
         return hit
 
     def _lo4_act(self, rows: int, width: int, heads: Optional[tuple] = None, sel: Optional[tuple] = None):
@@ -693,7 +751,7 @@ class LeopardEngine:
         ops.layernorm(x, W.post_ln_w, W.post_ln_b, out, vc.layer_norm_eps)
         return out
 
-    def _llm_layers_lo4(self, x, cache, cu, cos, sin, max_len, seq_lens=None, all_rows=False):
+    def _llm_layers_lo4(self, x, cache, cu, cos, sin, max_len, seq_lens=None, all_rows=False, extra_rows=None):
         """The Llama / Mistral layers with the low-bit correction phase, on the FUSED schedule of the fast path: the RMSNorms ride in the GEMM
         epilogues (the producers o_proj / down_proj also write the fp4 image of the residual of T(x gamma)), q|k|v + RoPE + KV append is one
         launch, gate/up's SwiGLU epilogue writes down_proj's operand pair, the attention kernel o_proj's: no launch is added to the fast schedule."""
@@ -706,7 +764,9 @@ class LeopardEngine:
         # row selection (lo4_rows): only the trailing rows of each sequence hand over residual images; the other rows' images stay zero and the
         # tiles without a selected row skip the fp4 k-tiles (csrc/gemm.h GemmArgs::row_sel)
         # (``all_rows``: the caller reads the logits of EVERY row — all_logits — so every row is a logits row)
-        sel = None if all_rows else self._lo4_selection(seq_lens if seq_lens is not None else [S])
+        # (``extra_rows``: packed rows whose logits are read besides the tails — score / score_batch: corrected too)
+        sel = None if all_rows else self._lo4_selection(seq_lens if seq_lens is not None else [S], extra_rows)
+        self.last_lo4_ranges = np.array([[0, S]], dtype=np.int32) if sel is None else sel[2].copy()
         h, att, gu = self._lo4_act(S, D, sel=sel), self._lo4_act(S, qw, heads=(H, hd), sel=sel), self._lo4_act(S, W.llm_ff, sel=sel)
         qkv = self._empty(S, qw + 2 * kw)
         parts = (D + 63) // 64
@@ -779,7 +839,7 @@ class LeopardEngine:
                     self.project(self.vision_tower(static_in, lo4_tiles), n)
                 torch.cuda.current_stream(self.device).wait_stream(side)
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with _capture_safe(), torch.cuda.graph(g):
                     static_out = self.project(self.vision_tower(static_in, lo4_tiles), n)
             finally:
                 self._private_scratch = False
@@ -814,9 +874,10 @@ class LeopardEngine:
     # a11: LLM prefill over one or several packed causal sequences
     # ------------------------------------------------------------------------------------------------
     def llm_prefill(self, x: torch.Tensor, seq_lens: Sequence[int], cache: Optional[KVCache] = None,
-                    all_logits: bool = False):
+                    all_logits: bool = False, score_rows: Optional[np.ndarray] = None):
         """x: fp32 [sum(seq_lens), D] residual stream (updated in place).  Returns (logits_last [n_seq, V],
-        logits_all or None).  ``cache`` (single sequence only) receives rotated K and V."""
+        logits_all or None).  ``cache`` (single sequence only) receives rotated K and V.  ``score_rows`` (score / score_batch): the packed
+        rows whose logits are read — the lo4 schedule corrects them as well — and no head runs here: returns (None, None)."""
         ops, W, tc = self.ops, self.W, self.cfg.text_config
         S, D = x.shape
         (H, KV), hd = self._llm_heads(), tc.head_dim
@@ -827,18 +888,19 @@ class LeopardEngine:
         if cache is not None:       # one sequence, or a pool holding the packed rows of several (generate_batch splits it afterwards)
             assert cache.length == 0 and cache.capacity >= S
         max_len = max(int(l) for l in seq_lens)
+        self.last_lo4_ranges = None
         if self.trace:
             self.trace("llm.embed", x)
         if self.fp8 is not None or ((self.split_operands or self.lo4) and self.tp_size == 1):
             if self.fp8 is not None:
                 self._llm_layers_fp8(x, cache, cu, cos, sin, max_len, seq_lens)
             elif self.lo4:
-                self._llm_layers_lo4(x, cache, cu, cos, sin, max_len, seq_lens, all_rows=all_logits)
+                self._llm_layers_lo4(x, cache, cu, cos, sin, max_len, seq_lens, all_rows=all_logits, extra_rows=score_rows)
             else:
                 self._llm_layers_split(x, cache, cu, cos, sin, max_len)
             if cache is not None:
                 cache.length = S
-            return self._lm_head(x, last_rows, all_logits)
+            return (None, None) if score_rows is not None else self._lm_head(x, last_rows, all_logits)
         parts = (D + 63) // 64
         total, offs = ops.llm_prefill_workspace(S, D, H, KV, hd, W.llm_ff, self.dtype)
         h, qkv, att, gu, sq_a, sq_b = self._carve("llm", total, offs, [(S, D, self.dtype), (S, qw + 2 * kw, self.dtype), (S, qw, self.dtype),
@@ -895,7 +957,7 @@ class LeopardEngine:
                     self.trace(f"llm.{i}", x)
         if cache is not None:
             cache.length = S
-        return self._lm_head(x, last_rows, all_logits)
+        return (None, None) if score_rows is not None else self._lm_head(x, last_rows, all_logits)
 
     def _llm_layers_fp8(self, x, cache, cu, cos, sin, max_len, seq_lens=None):
         """The Llama layers with fp8 linears (leopard_amd.fp8): RMSNorm -> fp8 operand in one launch, the SwiGLU epilogue of
@@ -1230,6 +1292,139 @@ class LeopardEngine:
         return last, seq_lens
 
     # ------------------------------------------------------------------------------------------------
+    # scoring: log-likelihoods of labelled tokens (EVAL:333-348, forward(labels=)) with the head over the scored rows only
+    # ------------------------------------------------------------------------------------------------
+    IGNORE_INDEX = -100                # LlavaConfig.ignore_index / nn.CrossEntropyLoss's default
+
+    def _host_labels(self, input_ids: torch.Tensor, labels) -> np.ndarray:
+        """labels -> host int64 [S_in] after the checks that must fail before any launch: the shape of input_ids, ids in [0, V) or -100."""
+        if labels is None:
+            raise ValueError("score needs labels (the shape of input_ids; -100 = not scored)")
+        lab = torch.as_tensor(labels).detach()
+        if tuple(lab.shape) != tuple(input_ids.shape):
+            raise ValueError(f"labels must have the shape of input_ids {tuple(input_ids.shape)}, got {tuple(lab.shape)}")
+        lab = lab.to("cpu", torch.int64).reshape(-1).numpy()
+        V = self.cfg.text_config.vocab_size
+        bad = np.nonzero((lab != self.IGNORE_INDEX) & ((lab < 0) | (lab >= V)))[0]
+        if len(bad):
+            raise ValueError(f"labels must be token ids in [0, {V}) or {self.IGNORE_INDEX}: labels[{int(bad[0])}] = {int(lab[bad[0]])}")
+        return lab
+
+    def _merged_labels(self, ids: np.ndarray, labels: np.ndarray) -> np.ndarray:
+        """transformers-4.38 ``_merge_input_ids_with_image_features`` with labels: every visual row gets the ignore index, each text label
+        goes to its merged row (the rows plan_merge gives the text positions)."""
+        is_img = ids == self.cfg.image_token_index
+        width = np.where(is_img, self.cfg.tokens_per_tile, 1)
+        start = np.cumsum(width) - width
+        merged = np.full(int(width.sum()), self.IGNORE_INDEX, dtype=np.int64)
+        merged[start[~is_img]] = labels[~is_img]
+        return merged
+
+    def score_targets(self, input_ids: torch.Tensor, labels) -> Tuple[np.ndarray, np.ndarray, int]:
+        """(rows, targets, S) on the host: merged row s is scored against merged label s + 1 (EVAL:337-343's shift) wherever that label is
+        not the ignore index.  Raises ValueError on bad labels (nothing is launched)."""
+        lab = self._host_labels(input_ids, labels)
+        merged = self._merged_labels(input_ids.detach().reshape(-1).to("cpu", torch.int64).numpy(), lab)
+        tgt = merged[1:]
+        rows = np.nonzero(tgt != self.IGNORE_INDEX)[0].astype(np.int64)
+        return rows, tgt[rows], len(merged)
+
+    def _request_visual(self, samples) -> List[Optional[torch.Tensor]]:
+        """Visual tokens of every (input_ids, tiles[, visual_tokens]) request: the tiles of all requests through ONE vision encode, as
+        prefill_batch does."""
+        tpt = self.cfg.tokens_per_tile
+        need = [(s[0], s[1]) for s in samples if (len(s) < 3 or s[2] is None) and s[1] is not None and s[1].shape[0] > 0]
+        visual = None
+        if need:
+            vflags = self.lo4_vit_tiles([t.shape[0] for _, t in need], [ids.numel() + t.shape[0] * (tpt - 1) for ids, t in need])
+            visual = self.encode_images(torch.cat([t for _, t in need], dim=0), vflags)
+        out, row = [], 0
+        for s in samples:
+            if len(s) > 2 and s[2] is not None:
+                out.append(s[2])
+            elif s[1] is not None and s[1].shape[0] > 0:
+                n = s[1].shape[0]
+                out.append(visual[row * tpt:(row + n) * tpt])
+                row += n
+            else:
+                out.append(None)
+        return out
+
+    def _score_head(self, x: torch.Tensor, rows: torch.Tensor, targets: torch.Tensor):
+        """Final RMSNorm of the gathered rows (lmi_rmsnorm_rows: the bits lmi_rmsnorm gives them) -> head GEMM into ONE reusable fp32 chunk of
+        at most ``score_chunk_rows`` rows -> lmi_token_logprobs.  Peak extra memory: about one chunk, whatever the number of rows."""
+        ops, W, tc = self.ops, self.W, self.cfg.text_config
+        n, D, Vp = rows.numel(), x.shape[1], W.lm_head.shape[0]
+        C = max(1, min(int(self.score_chunk_rows), n))
+        h = self._empty(C, D)
+        buf = self._empty(C, Vp, dtype=torch.float32)
+        lp, lse = self._empty(n, dtype=torch.float32), self._empty(n, dtype=torch.float32)
+        am = self._empty(n, dtype=torch.int64)
+        for c0 in range(0, n, C):
+            m = min(C, n - c0)
+            ops.rmsnorm_rows(x, rows[c0:c0 + m], W.final_norm, h[:m], tc.rms_norm_eps)
+            ops.gemm(h[:m], W.lm_head, buf[:m], epilogue=_lib.EPI_STORE_F32)
+            ops.token_logprobs(buf[:m], tc.vocab_size, targets[c0:c0 + m], lp[c0:c0 + m], lse[c0:c0 + m], am[c0:c0 + m])
+        return lp, am
+
+    @torch.no_grad()
+    def score(self, input_ids: torch.Tensor, tiles, labels, visual_tokens: Optional[torch.Tensor] = None) -> ScoreResult:
+        """Log-likelihoods of the labelled tokens of one request: ``labels`` [1, S_in] as input_ids, -100 = not scored (LlavaForConditional-
+        Generation.forward(labels=) semantics, EVAL:333-348: the 4.38 merge with labels, then merged row s predicts merged label s + 1).  The
+        head runs over the scored rows only, in chunks; under precision "lo4" the pass also corrects the scored rows.  No targets: loss nan
+        and no head launch."""
+        return self.score_batch([(input_ids, tiles, labels)], visual_tokens=[visual_tokens])[0]
+
+    @torch.no_grad()
+    def score_batch(self, requests: Sequence[tuple], visual_tokens: Optional[Sequence[Optional[torch.Tensor]]] = None) -> List[ScoreResult]:
+        """score() for several requests [(input_ids [1, S_in], tiles, labels)] in ONE packed varlen prefill (as prefill_batch); request i's
+        results are those of its own score() call, bit for bit.  All labels are checked before anything is launched."""
+        if self.tp_size > 1:
+            raise NotImplementedError("scoring runs on one rank (tensor-parallel engines: out of scope, as all_logits)")
+        plans = [self.score_targets(r[0], r[2]) for r in requests]
+        if not any(len(p[0]) for p in plans):                        # nothing labelled: nothing to compute (nn.CrossEntropyLoss gives nan)
+            return [self._empty_score(S) for _, _, S in plans]
+        vis = self._request_visual([(r[0], r[1], None if visual_tokens is None else visual_tokens[i]) for i, r in enumerate(requests)])
+        xs = [self.embed_merge(r[0], v) for r, v in zip(requests, vis)]
+        seq_lens = [x.shape[0] for x in xs]
+        for (_, _, S), l in zip(plans, seq_lens):
+            assert S == l
+        offs = np.cumsum([0] + seq_lens[:-1])
+        rows_all = np.concatenate([p[0] + o for p, o in zip(plans, offs)])
+        tgt_all = np.concatenate([p[1] for p in plans])
+        x = torch.cat(xs, dim=0) if len(xs) > 1 else xs[0]
+        self.llm_prefill(x, seq_lens, score_rows=rows_all)
+        rows_dev = torch.from_numpy(rows_all).to(self.device)
+        tgt_dev = torch.from_numpy(tgt_all).to(self.device)
+        lp, am = self._score_head(x, rows_dev, tgt_dev)
+        out, k = [], 0
+        for (rows, _, S), o in zip(plans, offs):
+            m = len(rows)
+            if m:
+                loss = (-lp[k:k + m].to(torch.float64).mean()).to(torch.float32)      # the mean over the request's targets (fp64 sum)
+                out.append(ScoreResult(loss, lp[k:k + m], am[k:k + m], tgt_dev[k:k + m], rows_dev[k:k + m] - int(o), S))
+            else:
+                out.append(self._empty_score(S))
+            k += m
+        return out
+
+    def logits_logprobs(self, logits: torch.Tensor, rows: np.ndarray, targets: np.ndarray):
+        """lmi_token_logprobs on rows of already computed fp32 logits [S, >= V] (forward(labels=): no second head pass).  Returns (token
+        logprobs fp32 [n], argmax int64 [n]) on the device."""
+        n = len(rows)
+        lp, lse = self._empty(n, dtype=torch.float32), self._empty(n, dtype=torch.float32)
+        am = self._empty(n, dtype=torch.int64)
+        if n:
+            self.ops.token_logprobs(logits, self.cfg.text_config.vocab_size, torch.from_numpy(np.ascontiguousarray(targets)).to(self.device), lp, lse,
+                                    am, rows=torch.from_numpy(np.ascontiguousarray(rows)).to(self.device))
+        return lp, am
+
+    def _empty_score(self, S: int) -> ScoreResult:
+        e = lambda dt: self._empty(0, dtype=dt)
+        return ScoreResult(torch.full((), float("nan"), dtype=torch.float32, device=self.device), e(torch.float32), e(torch.int64),
+                           e(torch.int64), e(torch.int64), S)
+
+    # ------------------------------------------------------------------------------------------------
     # a12: decode.  One step = ~290 launches of memory-bound kernels, so the step is captured once per KV cache into a
     # HIP graph over static buffers; the token id and the position live in device memory (lmi_rope_qk_at, device
     # cu_seqlens), the graph itself takes the argmax and advances the position, and the host only reads the new token.
@@ -1389,7 +1584,7 @@ class LeopardEngine:
             sent0 = self.comm.sent_bytes if self.comm is not None else 0
             try:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with _capture_safe(), torch.cuda.graph(g):
                     self._decode_body(st, cache)
             except Exception as exc:                   # a communicator that cannot be captured: run the step eagerly from now on
                 if self.tp_size == 1:
@@ -1652,7 +1847,7 @@ class LeopardEngine:
             for n, v in zip(names, keep):
                 getattr(st, n).copy_(v)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _capture_safe(), torch.cuda.graph(g):
                 self._batch_decode_body(st)
             for n, v in zip(names, keep):                              # capture does not execute
                 getattr(st, n).copy_(v)

@@ -275,6 +275,20 @@ class Idefics2Engine(LeopardEngine):
         g = gathered.view(R, per, Lt, D)
         return torch.cat([g[i % R, i // R] for i in range(n)], dim=0)
 
+    # ---- scoring (LeopardEngine.score / score_batch): tiles = the request's list of images --------------------------------------------
+    def _merged_labels(self, ids, labels):
+        """input_ids already hold one <image> id per visual row: the labels map 1:1 to the rows (Idefics2's own loss shifts them as given)."""
+        return np.asarray(labels, dtype=np.int64).copy()
+
+    def _request_visual(self, samples):
+        out = []
+        for s in samples:
+            if len(s) > 2 and s[2] is not None:
+                out.append(s[2])
+            else:
+                out.append(self.encode_images(s[1]) if s[1] is not None and len(s[1]) else None)
+        return out
+
     # ---- whole prefill (IDEF:91-95) ------------------------------------------------------------------------------
     @torch.no_grad()
     def prefill(self, input_ids: torch.Tensor, images: Optional[Sequence[torch.Tensor]], cache: Optional[KVCache] = None,

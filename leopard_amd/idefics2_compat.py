@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import json
 import os
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -246,6 +246,25 @@ class Idefics2ForConditionalGeneration:
                 continue
             imgs.append(x.to(torch.float32).contiguous())
         return imgs
+
+    @torch.no_grad()
+    def loglikelihood(self, requests, batch_size: int = 8) -> List[Tuple[float, bool]]:
+        """[(context_ids [1, S_c], continuation_ids [1, S_t], pixel_values)] -> [(sum log p(continuation | images + context), is_greedy)]:
+        as LeopardForConditionalGeneration.loglikelihood.  pixel_values: the processor's [1, n, 3, H, W] (unpadded as in generate; a
+        (pixel_values, pixel_attention_mask) pair is accepted too), a list of per-image [3, h, w] tensors, or None."""
+        from .compat import score_loglikelihood
+        P = self.config.vision_config.patch_size
+        reqs = []
+        for ctx, cont, pix in requests:
+            mask = None
+            if isinstance(pix, tuple):
+                pix, mask = pix
+            if pix is None or isinstance(pix, list):
+                imgs = pix
+            else:
+                imgs = self.unpad_images(pix, mask, self.patch_validity, P)
+            reqs.append((ctx, cont, None if imgs is None else [im.to(self.device) for im in imgs]))
+        return score_loglikelihood(self.engine, reqs, batch_size, self.device)
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, pixel_values=None, pixel_attention_mask=None, max_new_tokens: int = 128,

@@ -385,6 +385,26 @@ class Ops:
                                               w.stride(0), x_f32.stride(0), out.stride(0), _DT[w.dtype], self._stream(out)))
         return out
 
+    def rmsnorm_rows(self, x, rows, w, out, eps):
+        """out[r] = rmsnorm(x[rows[r]]) as lmi_rmsnorm computes it (lmi_rmsnorm_rows).  x: fp32 [S, D]; rows: int64 [n] on device; out: T [n, D]."""
+        n, D = out.shape
+        assert x.dtype == torch.float32 and rows.dtype == torch.int64 and rows.numel() == n and rows.is_contiguous() and x.shape[1] == D
+        self._check(self.lib.lmi_rmsnorm_rows(_ptr(x), _ptr(rows), _ptr(w), _ptr(out), n, D, x.stride(0), out.stride(0), float(eps),
+                                              _DT[out.dtype], self._stream(out)))
+        return out
+
+    def token_logprobs(self, logits, vocab, targets, logprob, lse, argmax, rows=None):
+        """lmi_token_logprobs: per row of fp32 ``logits`` [R, ld] (or of ``logits[rows]``): lse over the first ``vocab`` columns,
+        logprob = logit[target] - lse, argmax (lowest index on ties).  targets / rows: int64 [n]; logprob, lse: fp32 [n]; argmax: int64 [n]."""
+        n = targets.numel()
+        assert logits.dtype == torch.float32 and logits.stride(1) == 1 and targets.dtype == torch.int64 and targets.is_contiguous()
+        assert logprob.dtype == lse.dtype == torch.float32 and argmax.dtype == torch.int64
+        assert logprob.numel() >= n and lse.numel() >= n and argmax.numel() >= n and logprob.is_contiguous() and lse.is_contiguous()
+        assert rows is None or (rows.dtype == torch.int64 and rows.numel() == n and rows.is_contiguous())
+        assert rows is not None or logits.shape[0] >= n
+        self._check(self.lib.lmi_token_logprobs(_ptr(logits), _ptr(rows), _ptr(targets), n, int(vocab), logits.stride(0), _ptr(logprob), _ptr(lse),
+                                                _ptr(argmax), self._stream(logits)))
+
     def gemm_ex(self, a, w, out, bias=None, epilogue=EPI_STORE, act=ACT_NONE, rowsq_in=None, norm_dim=0, norm_eps=0.0, norm_out=None,
                 norm_gamma=None, rowsq_out=None):
         """lmi_gemm with the RMSNorm folded in: consumer side (rowsq_in: [M, parts] fp32 partial sums of squares -> rows scaled
