@@ -1,23 +1,28 @@
 #!/usr/bin/env python3
 """bench.py — Leopard-LLaVA multi-image prefill throughput on MI355X (the BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank/GPU)
+    python bench.py --gpus N --steps K --warmup W [--full]  (N>1: launched by torch.distributed.run, one rank/GPU)
+
+A plain run does what the headline figure needs — set-up, W warm-up steps, K timed steps, --dump-outputs, the line — and nothing else.
+--full adds every other measurement and check described below (the step from ready-made tiles and from host pixels, the GPU tiler
+against the host tiler, parity against the committed oracle fixtures, roofline, the fast schedule, cpu_baseline, "tp", the other
+BASELINE configurations): minutes instead of seconds, the same headline.
 
 A "step" is one pass of the hot path over one synthetic sample of BASELINE config C3 — 6 images of 1344x896 ->
 adaptive tiler (on the GPU) -> 42 ViT inputs (364x364) -> SigLIP-SO400M (27 layers) -> pixel-shuffle + projector -> 7098
 visual tokens merged into a 7187-token sequence -> Llama-3.1-8B prefill (32 layers, KV cache written) ->
 last-position logits ("tiler -> logits of last position").  The source pixels (u8 HWC) and the token ids
 are resident in HBM / on the host when the timed region starts; weights are seeded synthetic values of the real
-architecture (no checkpoints exist offline).  `ms_per_step_excl_tiler` times the same step from ready-made tiles.
+architecture (no checkpoints exist offline).  `ms_per_step_excl_tiler` (--full) times the same step from ready-made tiles.
 
 Multi-GPU (`--gpus N`, one rank per GPU): the headline shards by SAMPLE exactly as the reference does
 (run_eval_llava_siglip_multiimg.sh:9-11, one process per GPU over dataset shards, no collective on the data path): every
-rank prefills its own sample, per-GPU work is fixed ("weak" scaling), value = ranks x images / max-over-ranks time.  The
-same line also carries `"tp"`: ONE sample per step on all ranks (tile-sharded ViT + all-gather, sequence-parallel
+rank prefills its own sample, per-GPU work is fixed ("weak" scaling), value = ranks x images / max-over-ranks time.  With
+--full the same line also carries `"tp"`: ONE sample per step on all ranks (tile-sharded ViT + all-gather, sequence-parallel
 tensor-parallel LLM over RCCL; strong scaling), measured after the headline in one child process per rank (a crash or hang
 there costs the `tp` object, not the line); `--parallelism tp` makes it the headline.  `backend`, `rccl_ranks` and `comm_bytes_per_step` say what carried the ranks.
 
-One JSON line on rank 0:  metric/value/unit + roofline (dominant kernel = the MFMA GEMM family incl. its fused norm / RoPE
+One JSON line on rank 0:  metric/value/unit (+ what the set-up and the timed steps give for free); with --full + roofline (dominant kernel = the MFMA GEMM family incl. its fused norm / RoPE
 epilogues, HIP-event timed on the launch stream; `dominant` = the single largest shape) + cpu_baseline (the CPU oracle's
 end-to-end C1 prefill on the host cores, plus the C3 figure extrapolated from a bounded sample).
 """
@@ -448,7 +453,7 @@ def bench_c5(args, dev, dtype, rank, world, D):
     out = {"metric": "multi-image prefill images/sec (Leopard-LLaVA, batch 8 x 8 x 1344x896)",
            "value": round(world * n_samples * n_img * args.steps / elapsed, 3), "unit": "images/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+           "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
            **({"dtype_detail": fp8_detail(args), "accuracy_note": FP8_ACCURACY_NOTE} if args.dtype == "fp8" else {}),
            "config": {"workload": f"C5 shape: {n_samples} samples x {n_img} x (1344x896) -> {n_tiles} ViT inputs, "
                                   f"{sum(seq_lens)} tokens packed in one varlen pass; SigLIP-SO400M + Llama-3.1-8B prefill to "
@@ -532,7 +537,7 @@ def bench_idefics2(args, dev, dtype, rank, world, D):
            "value": round((1 if tp else world) * n_img * args.steps / elapsed, 3), "unit": "images/s", "n_gpus": world, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
            "scaling": "strong" if tp else "weak",
-           "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "precision_mode": PRECISION_NOTE[idef_precision],
+           "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full, "precision_mode": PRECISION_NOTE[idef_precision],
            "config": {"workload": f"C4: 4x(1344x896) -> 980x653, 3220 patches each, 64 visual tokens each, S={S}; NaViT SigLIP (27L) + "
                                   "perceiver (3L) + Mistral-7B (32L) prefill to last-token logits; synthetic seeded weights",
                       "parallelism": (f"one sample on {world} ranks: images round-robin + 1 all-gather; TP{world} Mistral with sequence-parallel norms"
@@ -541,7 +546,7 @@ def bench_idefics2(args, dev, dtype, rank, world, D):
            "prefill_mfma_frac": round(total / 1e12 / (elapsed / args.steps) / (MFMA_PEAK_TFLOPS * (world if tp else 1)), 4)}
     if tp:
         out.update({"backend": eng.comm.backend, "rccl_ranks": eng.comm.ranks_seen(), "comm_bytes_per_step": int(eng.comm.sent_bytes / (args.steps + args.warmup)) * world})
-    if rank == 0 and seed == 0 and args.dtype == "f16":
+    if rank == 0 and seed == 0 and args.dtype == "f16" and args.full:
         out["parity"] = idefics2_fixture_parity(ids, imgs, res)
     if rank == 0 and not tp and not args.no_roofline:
         out["roofline"] = roofline_from_timer(ops, step, 1, False)
@@ -625,7 +630,7 @@ def measure_tp(args, cfg, ops, dev, dtype, rank, world, D, gpu_tiler):
     pc = _Ctx()
     pc.ids, pc.tiles = ids, torch.from_numpy(u8)
     return {"value": round(args.images * args.steps / elapsed, 3), "unit": "images/s", "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "parity": fixture_parity(args, pc, res) if rank == 0 else None,
+            "parity": fixture_parity(args, pc, res) if rank == 0 and args.full else None,
             "scaling": "strong", "n_gpus": world, "precision_mode": PRECISION_NOTE[tp_precision],
             "parallelism": f"one sample on {world} ranks: ViT inputs sharded {u8.shape[0]} -> {world} + 1 all-gather; TP{world} LLM with "
                            f"sequence-parallel norms ({eng.tp_chunks} row chunks, all-gather + reduce-scatter per half layer in "
@@ -679,7 +684,7 @@ def run_other_configs(cpu_tflops: float, timeout_s: float = 240.0) -> dict:
             "graph_encode", "dtype_detail", "accuracy_note", "lo4_rows")
     res = {}
     for key, what, argv in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--no-other-configs", "--no-fast-line", "--no-cpu-baseline", "--cpu-tflops", f"{cpu_tflops:.4f}"] + argv
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-other-configs", "--no-fast-line", "--no-cpu-baseline", "--cpu-tflops", f"{cpu_tflops:.4f}"] + argv
         t0 = time.perf_counter()
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
@@ -713,7 +718,7 @@ def run_tp_child(args, rank, world, D, dev) -> dict:
     env = {k: v for k, v in os.environ.items() if not k.startswith("TORCHELASTIC_")}      # the child is its own rendezvous, not the agent's
     env["MASTER_PORT"] = str(port)
     env.setdefault("MASTER_ADDR", "127.0.0.1")
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--parallelism", "tp", "--steps", str(args.steps), "--warmup",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--gpus", str(world), "--parallelism", "tp", "--steps", str(args.steps), "--warmup",
            str(args.warmup), "--dtype", args.dtype, "--images", str(args.images), "--width", str(args.width), "--height", str(args.height)]
     if args.precision in ("fast", "lo4"):
         cmd += ["--precision", args.precision]
@@ -765,7 +770,15 @@ def dump_outputs(out_dir: str, ctxs, rank: int, world: int) -> None:
             np.save(os.path.join(out_dir, f"{name}{tag}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
-def main():
+def plain_run(args) -> None:
+    """Without --full a run does what its headline figure needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs, the
+    line.  Every further measurement or check (the --no-* options name most of them; the rest ask args.full) is switched off here."""
+    if not args.full:
+        args.no_roofline = args.no_fast_line = args.no_cpu_baseline = args.no_tp = args.no_other_configs = True
+        args.cpu_tflops = 0.0
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -809,11 +822,23 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (last-position logits + a fixed sample of the KV "
                          "cache it wrote) as DIR/<name>.npy, for output-by-output comparison of two builds (llava-c3, --parallelism sample)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else the line can carry: the GPU tiler against the host tiler, the step "
+                         "from ready-made tiles and from host pixels, parity against the committed oracle fixtures, the GEMM roofline, the fast "
+                         "schedule, the CPU baseline, the tensor-parallel figure (N > 1) and the other BASELINE configurations (minutes; each of "
+                         "--no-roofline / --no-fast-line / --no-cpu-baseline / --no-tp / --no-other-configs takes its part out again).  Without "
+                         "--full a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    args = ap.parse_args(argv)
+    plain_run(args)
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and (args.workload != "llava-c3" or args.parallelism != "sample"):
         raise SystemExit("--dump-outputs is implemented for the llava-c3 workload with --parallelism sample")
+    return args
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -854,7 +879,7 @@ def main():
         r = measure_tp(args, cfg, ops, dev, dtype, rank, world, D, GpuTiler(ops, dev))
         out = {"metric": metric_name(args), "value": r["value"], "unit": "images/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"], "higher_is_better": True,
-               "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+               "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
                "config": {"workload": f"{config_label(args)}: {args.images}x({args.width}x{args.height}) images, one sample per step on all ranks",
                           "parallelism": r["parallelism"]},
                "backend": r["backend"], "rccl_ranks": r["rccl_ranks"], "comm_bytes_per_step": r["comm_bytes_per_step_per_rank"] * world,
@@ -902,7 +927,7 @@ def main():
         c.tiles, _ = gpu_tiler.tile_sample(c.raw)                  # the tiler on the GPU (a3-a5), from resident source pixels
         torch.cuda.synchronize()
         gpu_tiler_s = max(gpu_tiler_s, time.perf_counter() - t1)
-        if not torch.equal(c.tiles.cpu(), torch.from_numpy(u8)):   # same pixels as the host (PIL) tiler, bit for bit
+        if args.full and not torch.equal(c.tiles.cpu(), torch.from_numpy(u8)):   # same pixels as the host (PIL) tiler, bit for bit
             raise SystemExit("GPU tiler differs from the host tiler")
         c.ids = torch.from_numpy(ids_np).reshape(1, -1)            # token ids stay host-side, like a tokenizer's output
         c.n_tiles = u8.shape[0]
@@ -945,26 +970,28 @@ def main():
     if args.dump_outputs:                                          # before anything else runs on these caches
         dump_outputs(args.dump_outputs, ctxs, rank, world)
     ms_per_step = elapsed / args.steps * 1e3
-    # the same step from ready-made tiles (what round 1 timed): the tiler's share of the headline
-    n_ex = max(2, min(args.steps, 5))
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(n_ex):
-        step(with_tiler=False)
-    barrier()
-    ms_excl_tiler = D.max_over_ranks(time.perf_counter() - t0, dev) / n_ex * 1e3
-    # and from source pixels that start in HOST memory (what a caller holding decoded images hands over): the same step plus the
-    # PCIe copy of the images — reported beside the headline, never as `value`
-    host_raw = [[np.array(r) for r in c.raw_host] for c in ctxs]
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(n_ex):
-        for c, hr in zip(ctxs, host_raw):
-            with torch.cuda.stream(c.stream):
-                c.cache.length = 0
-                eng.prefill(c.ids, gpu_tiler.tile_sample(hr)[0], cache=c.cache)
-    barrier()
-    ms_from_host = D.max_over_ranks(time.perf_counter() - t0, dev) / n_ex * 1e3
+    ms_excl_tiler = ms_from_host = None
+    if args.full:
+        # the same step from ready-made tiles (what round 1 timed): the tiler's share of the headline
+        n_ex = max(2, min(args.steps, 5))
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(n_ex):
+            step(with_tiler=False)
+        barrier()
+        ms_excl_tiler = D.max_over_ranks(time.perf_counter() - t0, dev) / n_ex * 1e3
+        # and from source pixels that start in HOST memory (what a caller holding decoded images hands over): the same step plus the
+        # PCIe copy of the images — reported beside the headline, never as `value`
+        host_raw = [[np.array(r) for r in c.raw_host] for c in ctxs]
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(n_ex):
+            for c, hr in zip(ctxs, host_raw):
+                with torch.cuda.stream(c.stream):
+                    c.cache.length = 0
+                    eng.prefill(c.ids, gpu_tiler.tile_sample(hr)[0], cache=c.cache)
+        barrier()
+        ms_from_host = D.max_over_ranks(time.perf_counter() - t0, dev) / n_ex * 1e3
     images_per_s = world * args.inflight * args.images * args.steps / elapsed
     fl = algorithmic_flops(cfg, n_tiles, S)
 
@@ -989,14 +1016,14 @@ def main():
         "algorithmic_tflop_per_step": round(args.inflight * fl["total"] / 1e12, 2),
         "prefill_mfma_frac": round(args.inflight * fl["total"] / 1e12 / (elapsed / args.steps) / MFMA_PEAK_TFLOPS, 4),
         "timed_region": "tiler (GPU, from source pixels resident in HBM) -> ViT -> projector -> merge -> LLM prefill -> last-token logits",
-        "ms_per_step_excl_tiler": round(ms_excl_tiler, 3),
-        "ms_per_step_from_host_pixels": round(ms_from_host, 3),
-        "images_per_s_from_host_pixels": round(world * args.inflight * args.images / (ms_from_host * 1e-3), 3),
+        **({"ms_per_step_excl_tiler": round(ms_excl_tiler, 3),
+            "ms_per_step_from_host_pixels": round(ms_from_host, 3),
+            "images_per_s_from_host_pixels": round(world * args.inflight * args.images / (ms_from_host * 1e-3), 3)} if args.full else {}),
         "host_tiler_ms_per_sample": round(host_tiler_s * 1e3, 1), "gpu_tiler_ms_per_sample": round(gpu_tiler_s * 1e3, 2),
-        "weight_load_s": round(load_s, 1),
+        "weight_load_s": round(load_s, 1), "full": args.full,
     }
 
-    if rank == 0:
+    if rank == 0 and args.full:
         out["parity"] = fixture_parity(args, ctxs[0], res if args.inflight == 1 else None)
     if rank == 0 and not args.no_roofline:
         def once():

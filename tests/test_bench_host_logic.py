@@ -162,3 +162,48 @@ def test_dump_outputs_writes_the_last_step_within_the_size_bound(monkeypatch, tm
     names = sorted(os.listdir(tmp_path / "c"))
     assert len(names) == 12 and "kv_v_rank1_sample3.npy" in names
     assert 2 * sum(os.path.getsize(tmp_path / "c" / f) for f in names) <= bench.DUMP_BYTES
+
+
+def test_a_plain_run_switches_every_extra_off_and_full_leaves_them_on():
+    """bench.py without --full does what the headline needs and nothing else: every further measurement is off whatever else the command
+    says; with --full each of them runs unless its own --no-* option takes it out, as before the option existed."""
+    extras = ("no_roofline", "no_fast_line", "no_cpu_baseline", "no_tp", "no_other_configs")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--cpu-tflops", "0.5"])
+    assert plain.full is False and all(getattr(plain, k) for k in extras) and plain.cpu_tflops == 0.0
+    assert (plain.steps, plain.warmup, plain.dump_outputs) == (3, 1, None)
+    full = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert full.full is True and not any(getattr(full, k) for k in extras)
+    part = bench.parse_args(["--full", "--no-roofline", "--no-other-configs", "--cpu-tflops", "0.5"])
+    assert part.no_roofline and part.no_other_configs and not part.no_fast_line and not part.no_cpu_baseline and part.cpu_tflops == 0.5
+
+
+def test_child_runs_of_the_full_line_ask_for_full(monkeypatch):
+    """The other BASELINE configurations and the tensor-parallel figure are child runs of bench.py whose entries carry parity, roofline and
+    cpu_baseline: the children are started with --full (and the --no-* options that keep them from recursing)."""
+    import json
+    import subprocess
+    import sys
+    cmds = []
+
+    def fake_run(cmd, **kw):
+        cmds.append(cmd)
+        line = {"value": 1.0, "unit": "images/s", "ms_per_step": 2.0, "config": {"workload": "w"}, "parity": {"normalised_max": 1e-4},
+                "roofline": {"bound": "mfma", "frac": 0.4}, "cpu_baseline": {"value": 0.1}}
+        return types.SimpleNamespace(returncode=0, stdout=json.dumps(line) + "\n", stderr="")
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    res = bench.run_other_configs(0.5)
+    assert len(cmds) == len(bench.OTHER_CONFIGS) and set(res) == {k for k, _, _ in bench.OTHER_CONFIGS}
+    for cmd in cmds:
+        assert "--full" in cmd and "--no-other-configs" in cmd and "--no-cpu-baseline" in cmd and cmd[cmd.index("--cpu-tflops") + 1] == "0.5000"
+        child = bench.parse_args(cmd[2:])
+        assert child.full and not child.no_roofline and child.cpu_tflops == 0.5
+    assert all(e["parity"] and e["roofline"]["frac"] == 0.4 and e["cpu_baseline"] for e in res.values())
+    seen = {}
+    real_popen = subprocess.Popen
+
+    def fake_popen(cmd, **kw):
+        seen["cmd"] = cmd
+        return real_popen([sys.executable, "-c", "print('{\"tp\": {\"value\": 2.0}}')"], **kw)
+    monkeypatch.setattr(subprocess, "Popen", fake_popen)
+    assert bench.run_tp_child(_tp_args(), 0, 2, _FakeD, None) == {"value": 2.0}
+    assert "--full" in seen["cmd"] and bench.parse_args(seen["cmd"][2:]).parallelism == "tp"
