@@ -141,8 +141,7 @@ class LeopardForConditionalGeneration:
                 raise NotImplementedError("labels score a whole prompt: no past_key_values")
             rows, targets, _ = eng.score_targets(input_ids, labels)          # ValueError on bad labels, before any launch
         tiles = self._as_tiles(pixel_values)
-        S = input_ids.shape[1] + int((input_ids == self.config.image_token_index).sum()) * (self.config.tokens_per_tile - 1)
-        cache = KVCache(self.config, S + 256, self.compute_dtype, self.device) if use_cache else None
+        cache = KVCache(self.config, eng.merged_len(input_ids) + 256, self.compute_dtype, self.device) if use_cache else None
         res = eng.prefill(input_ids.to(self.device), tiles, cache=cache, all_logits=True)
         loss = None
         if labels is not None:

@@ -102,6 +102,7 @@ class KVCache:
         self.k = [torch.zeros(capacity, w, dtype=dtype, device=device) for _ in range(tc.num_hidden_layers)]
         self.v = [torch.zeros(capacity, w, dtype=dtype, device=device) for _ in range(tc.num_hidden_layers)]
         self.capacity, self.length = capacity, 0
+        self._decode_state = None                # the DecodeState of the batch-1 step over this cache (LeopardEngine._decode_state)
 
 
 @dataclass
@@ -146,6 +147,59 @@ def _capture_safe():
 
 def _signed64(v: int) -> int:
     return v - (1 << 64) if v >= (1 << 63) else v
+
+
+@dataclass(eq=False)
+class DecodeState:
+    """Static buffers, device counters and captured graphs of one decode step over B rows: the batch-1 step of one KVCache
+    (LeopardEngine._decode_state, kept on the cache) or the B slots of a pooled cache (LeopardEngine._batch_state)."""
+    B: int
+    capacity: int                                # KV rows per sequence the step's launch geometry is built for
+    mode: tuple                                  # (precision, decode_precision) the buffers and launches belong to: another mode rebuilds the state
+    layout: bool                                 # llm_packed at construction: a captured step replays the launches of that weight layout
+    hl: bool                                     # operand buffers hold [hi rows; lo rows] pairs (decode precision mode, decode_hl)
+    tok: torch.Tensor                            # int64 [B]: the token each row consumes; the step leaves the next one here
+    src: torch.Tensor                            # int64 [B] = 0 .. B-1: row b of the stream is the embedding of tok[b] (lmi_embed_merge)
+    pos: torch.Tensor                            # int32 [B]
+    cu_q: torch.Tensor                           # int32 [B + 1]: one query row per sequence
+    k_begin: torch.Tensor                        # int32 [B]: first cache row of each sequence, b * capacity
+    x: torch.Tensor                              # fp32 [B, D] residual rows
+    h: torch.Tensor
+    qkv: torch.Tensor
+    att: torch.Tensor
+    gu: torch.Tensor
+    hf32: Optional[torch.Tensor]                 # fp32 [B, D] (hl only): a norm's output before it is split into a pair
+    cos: torch.Tensor
+    sin: torch.Tensor
+    ws: torch.Tensor                             # decode attention workspace (lmi_decode_workspace_elems)
+    # per-row sampling parameters in device memory: written before a replay, read by the captured step, so new parameters never need a
+    # new capture.  ``sampling`` selects which of the two captured steps runs (``graph`` / ``graph_s``)
+    temp: torch.Tensor
+    topk: torch.Tensor
+    topp: torch.Tensor
+    seed: torch.Tensor
+    step: torch.Tensor
+    sampling: bool = False
+    graph: Optional[torch.cuda.CUDAGraph] = None       # the captured greedy step
+    graph_s: Optional[torch.cuda.CUDAGraph] = None     # the captured sampled step
+    graph_failed: bool = False                   # tensor parallel: the capture failed once, the step runs eagerly (_decode_run)
+    graph_comm_bytes: int = 0                    # tensor parallel: what one replay puts on the links
+    sq_a: Optional[torch.Tensor] = None          # folded-norm partials: feeding gate/up ...
+    sq_b: Optional[torch.Tensor] = None          # ... and the next layer's q|k|v
+    logits: Optional[torch.Tensor] = None        # fp32 [Vp] (batch-1 step) / [B, Vp]
+    # the batch-1 step of one KVCache only
+    cu_k: Optional[torch.Tensor] = None          # int32 [2]: [0, key count]
+    part: Optional[torch.Tensor] = None          # tensor parallel: partial o_proj / down_proj row
+    # the pooled step only: B slots of capacity rows per layer (slot b = rows [b * capacity, (b + 1) * capacity)) and the device side of
+    # continuous batching (_batch_state)
+    k: Optional[List[torch.Tensor]] = None
+    v: Optional[List[torch.Tensor]] = None
+    k_len: Optional[torch.Tensor] = None
+    live: Optional[torch.Tensor] = None
+    budget: Optional[torch.Tensor] = None
+    eos: Optional[torch.Tensor] = None
+    hist: Optional[torch.Tensor] = None
+    hist_pos: Optional[torch.Tensor] = None
 
 
 class LeopardEngine:
@@ -227,6 +281,12 @@ class LeopardEngine:
         self._inv_freq = llama3_inv_freq(tc.head_dim, tc.rope_theta, tc.rope_scaling).to(self.device)
         self._geom_cache: Dict[tuple, tuple] = {}      # seq_lens -> (cu, cos, sin, last_rows) device tensors
         self._vit_cu_cache: Dict[int, torch.Tensor] = {}
+        self._split_w = None           # [W | W] weight copies of the split-operand mode (_split_weights)
+        self._gen_cache = None         # the KV cache generate() reuses (_generation_cache)
+        self._stream_cache = None      # the KV cache generate_stream prefills a newcomer into before its rows move to a slot
+        self._batch_states: Dict[int, DecodeState] = {}   # B -> state of the batched decode step (_batch_state)
+        self._skinny_pack = None       # second copy of the LLM weights in the skinny-M operand order (_skinny_weights)
+        self._head_pack = None         # lm_head in the packed order (_skinny_head)
         # ONE copy of the LLM weights (default; LMI_PACK_LLM_WEIGHTS=0 / pack_llm_weights=False keep the nn.Linear layout): see pack_llm_weights
         if pack_llm_weights is None:
             pack_llm_weights = os.environ.get("LMI_PACK_LLM_WEIGHTS", "1") == "1"
@@ -462,22 +522,34 @@ class LeopardEngine:
         the lo4 schedule corrects the tower's linears for it (lo4_vit_tiles; None = none)."""
         ops, W, vc = self.ops, self.W, self.cfg.vision_config
         n = tiles.shape[0]
-        T, D, H, hd = vc.num_patches, vc.hidden_size, vc.num_attention_heads, vc.head_dim
+        T, D = vc.num_patches, vc.hidden_size
         M = n * T
         x = self._empty(M, D, dtype=torch.float32)
         # normalise + im2col + patch conv + bias + position embedding: one launch, no im2col matrix in HBM (lmi_patch_embed)
         ops.patch_embed(tiles, W.patch_w_fused, W.patch_b, W.pos_emb, x, vc.image_size, vc.patch_size)
-        cu = self._vit_cu_cache.get(n)
-        if cu is None:
-            cu = self._vit_cu_cache[n] = torch.arange(0, (n + 1) * T, T, dtype=torch.int32, device=self.device)
+        if n not in self._vit_cu_cache:          # cu_seqlens of the layers' attention: one T-token sequence per ViT input
+            self._vit_cu_cache[n] = torch.arange(0, (n + 1) * T, T, dtype=torch.int32, device=self.device)
         if self.trace:
             self.trace("vit.embed", x)
         if self.fp8 is not None:
-            return self._vit_layers_fp8(x, n)
-        if self.split_operands:
-            return self._vit_layers_split(x, n)
-        if self.lo4 and lo4_tiles is not None and any(lo4_tiles):
-            return self._vit_layers_lo4(x, n, lo4_tiles)
+            self._vit_layers_fp8(x, n)
+        elif self.split_operands:
+            self._vit_layers_split(x, n)
+        elif self.lo4 and lo4_tiles is not None and any(lo4_tiles):
+            self._vit_layers_lo4(x, n, lo4_tiles)
+        else:
+            self._vit_layers_fast(x, n)
+        out = self._empty(M, D)                 # a result, not scratch: the caller may hold it across later passes that reuse the workspace
+        ops.layernorm(x, W.post_ln_w, W.post_ln_b, out, vc.layer_norm_eps)
+        return out
+
+    def _vit_layers_fast(self, x: torch.Tensor, n: int) -> None:
+        """The SigLIP layers of the fast schedule (one rounding per operand hand-over), on the caller-owned workspace.  Like its siblings
+        below: updates the fp32 stream ``x`` in place."""
+        ops, W, vc = self.ops, self.W, self.cfg.vision_config
+        T, D, H, hd = vc.num_patches, vc.hidden_size, vc.num_attention_heads, vc.head_dim
+        M = n * T
+        cu = self._vit_cu_cache[n]
         qkv_w = W.vit_layers[0].qkv_w.shape[0] if W.vit_layers else 3 * D
         total, offs = ops.vit_workspace(M, D, qkv_w, W.vit_ff, self.dtype)
         h, qkv, att, ff = self._carve("vit", total, offs, [(M, D, self.dtype), (M, qkv_w, self.dtype), (M, D, self.dtype), (M, W.vit_ff, self.dtype)])
@@ -498,11 +570,8 @@ class LeopardEngine:
             ops.gemm(ff, L.fc2_w, x, bias=L.fc2_b, epilogue=_lib.EPI_RESIDUAL)
             if self.trace:
                 self.trace(f"vit.{li}", x)
-        out = self._empty(M, D)                 # a result, not scratch: the caller may hold it across later passes that reuse the workspace
-        ops.layernorm(x, W.post_ln_w, W.post_ln_b, out, vc.layer_norm_eps)
-        return out
 
-    def _vit_layers_fp8(self, x: torch.Tensor, n: int) -> torch.Tensor:
+    def _vit_layers_fp8(self, x: torch.Tensor, n: int) -> None:
         """The SigLIP layers with fp8 linears (leopard_amd.fp8): LayerNorm -> fp8 operand in one launch, fc1's GELU epilogue
         writes fc2's fp8 operand; q|k|v and the attention stay 16-bit, the residual stream fp32."""
         ops, W, vc, P = self.ops, self.W, self.cfg.vision_config, self.fp8
@@ -533,14 +602,11 @@ class LeopardEngine:
             ops.gemm_fp8(ff8, Q.lin["fc2"].w8, x, bias=L.fc2_b, epilogue=_lib.EPI_RESIDUAL, scale_exp=Q.out_exp("ff", "fc2"))
             if self.trace:
                 self.trace(f"vit.{li}", x)
-        h = self._empty(M, D)
-        ops.layernorm(x, W.post_ln_w, W.post_ln_b, h, vc.layer_norm_eps)
-        return h
 
     # ---- split-operand precision mode -------------------------------------------------------------------------------------------
     def _split_weights(self):
         """[W | W] copies of the layer-linear weights (K doubled), built on first use: +0.8 GB (SigLIP) + 14 GB (Llama-3.1-8B)."""
-        sw = getattr(self, "_split_w", None)
+        sw = self._split_w
         if sw is None:
             from .weights import as_row_major
             dup = lambda w: (lambda r: torch.cat([r, r], dim=1).contiguous())(as_row_major(w))
@@ -550,7 +616,7 @@ class LeopardEngine:
                 "llm": [(dup(L.qkv_w_rope if L.qkv_w_rope is not None else L.qkv_w), dup(L.o_w), dup(L.gu_w), dup(L.down_w)) for L in W.llm_layers]}
         return sw
 
-    def _vit_layers_split(self, x: torch.Tensor, n: int) -> torch.Tensor:
+    def _vit_layers_split(self, x: torch.Tensor, n: int) -> None:
         """The SigLIP layers with split (hi + lo) A operands: LayerNorm -> fp32 -> [hi | lo]; attention output and GELU output in fp32 ->
         [hi | lo]; every linear at 2 K against [W | W].  q / k / v and the attention arithmetic stay 16-bit."""
         ops, W, vc = self.ops, self.W, self.cfg.vision_config
@@ -576,9 +642,6 @@ class LeopardEngine:
             ops.gemm(ff2, fc2_w2, x, bias=L.fc2_b, epilogue=_lib.EPI_RESIDUAL)
             if self.trace:
                 self.trace(f"vit.{li}", x)
-        h = self._empty(M, D)
-        ops.layernorm(x, W.post_ln_w, W.post_ln_b, h, vc.layer_norm_eps)
-        return h
 
     def _llm_layers_split(self, x, cache, cu, cos, sin, max_len):
         """The Llama / Mistral layers with split (hi + lo) A operands (see _vit_layers_split); q|k|v + RoPE + KV append stay one launch
@@ -651,60 +714,50 @@ class LeopardEngine:
             return seq_len if seq_len <= self.LO4_FULL_BELOW else min(self.LO4_TAIL_ROWS, seq_len)
         return max(1, min(int(r), seq_len))
 
+    def _selection_tables(self, row: np.ndarray, pinned: bool):
+        """uint8 row mask [S] -> (row_sel [S], unit_sel [ceil(S / 64)]) device tensors + the host [n, 2] int32 array of the selected row
+        ranges (the maximal runs of ones: the tile-order hint of lmi_lo4.sel_ranges).  ``pinned``: staged through pinned memory and copied
+        asynchronously (tables cached per geometry and read on whatever stream the pass runs); otherwise a synchronous copy, ready before
+        any stream reads them (tables cached per launch stream)."""
+        S = len(row)
+        unit = np.zeros((S + 63) // 64 * 64, dtype=np.uint8)
+        unit[:S] = row
+        unit = unit.reshape(-1, 64).max(axis=1)
+        ranges = np.flatnonzero(np.diff(np.concatenate([[0], row.astype(np.int8), [0]]))).reshape(-1, 2)
+        to_device = self._pinned_to_device if pinned else (lambda t: t.to(self.device))
+        return to_device(torch.from_numpy(row)), to_device(torch.from_numpy(unit)), np.ascontiguousarray(ranges.astype(np.int32))
+
     def _lo4_selection(self, seq_lens: Sequence[int], extra_rows: Optional[np.ndarray] = None):
         """(row_sel uint8 [S], unit_sel uint8 [ceil(S / 64)]) device tensors + the host [n, 2] int32 array of the selected row ranges (the
         tile-order hint of lmi_lo4.sel_ranges) for the packed rows of ``seq_lens``, or None when every row is selected.  ``extra_rows``:
         packed rows whose logits are read besides the tails (the scored rows of score / score_batch): selected as well."""
-        tails = [self.lo4_tail_rows(int(l)) for l in seq_lens]
-        if all(t == int(l) for t, l in zip(tails, seq_lens)):
+        lens = tuple(int(l) for l in seq_lens)
+        tails = tuple(self.lo4_tail_rows(l) for l in lens)
+        if tails == lens:
             return None
         if extra_rows is not None and len(extra_rows):
-            return self._lo4_selection_extra(seq_lens, tails, np.asarray(extra_rows, dtype=np.int64))
-        key = (tuple(int(l) for l in seq_lens), tuple(tails))
-        hit = self._lo4_sel_cache.get(key)
+            # the tails united with the scored rows.  The tables are built with a synchronous copy (ready before any stream reads them) and
+            # cached per launch stream, under a key that holds the extra rows themselves
+            extra = np.asarray(extra_rows, dtype=np.int64)
+            sid = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+            cache, bound, key = self._score_sel_cache, 16, (sid, lens, tails, extra.tobytes())
+        else:
+            extra = None
+            cache, bound, key = self._lo4_sel_cache, 64, (lens, tails)
+        hit = cache.get(key)
         if hit is None:
-            S = int(sum(key[0]))
-            row = np.zeros(S, dtype=np.uint8)
-            end, ranges = 0, []
-            for l, t in zip(*key):
-                end += l
-                row[end - t:end] = 1
-                if ranges and ranges[-1][1] == end - t:
-                    ranges[-1][1] = end
-                else:
-                    ranges.append([end - t, end])
-            unit = np.zeros((S + 63) // 64 * 64, dtype=np.uint8)
-            unit[:S] = row
-            unit = unit.reshape(-1, 64).max(axis=1)
-            if len(self._lo4_sel_cache) >= 64:
-                self._lo4_sel_cache.pop(next(iter(self._lo4_sel_cache)))
-            hit = self._lo4_sel_cache[key] = (self._pinned_to_device(torch.from_numpy(row)), self._pinned_to_device(torch.from_numpy(unit)),
-                                              np.ascontiguousarray(np.array(ranges, dtype=np.int32).reshape(-1, 2)))
-        return hit
-
-    def _lo4_selection_extra(self, seq_lens, tails, extra: np.ndarray):
-        """_lo4_selection of the tails united with ``extra``.  The tables are built with a synchronous copy (ready before any stream reads
-        them) and cached per launch stream, under a key that holds the extra rows themselves."""
-        sid = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
-        key = (sid, tuple(int(l) for l in seq_lens), tuple(tails), extra.tobytes())
-        hit = self._score_sel_cache.get(key)
-        if hit is None:
-            S = int(sum(key[1]))
-            row = np.zeros(S, dtype=np.uint8)
+            row = np.zeros(sum(lens), dtype=np.uint8)
             end = 0
-            for l, t in zip(key[1], tails):
+            for l, t in zip(lens, tails):
                 end += l
                 row[end - t:end] = 1
-            row[extra] = 1
-            if row.all():
-                return None
-            unit = np.zeros((S + 63) // 64 * 64, dtype=np.uint8)
-            unit[:S] = row
-            ranges = np.flatnonzero(np.diff(np.concatenate([[0], row.astype(np.int8), [0]]))).reshape(-1, 2)
-            if len(self._score_sel_cache) >= 16:
-                self._score_sel_cache.pop(next(iter(self._score_sel_cache)))
-            hit = self._score_sel_cache[key] = (torch.from_numpy(row).to(self.device), torch.from_numpy(unit.reshape(-1, 64).max(axis=1)).to(self.device),
-                                                np.ascontiguousarray(ranges.astype(np.int32)))
+            if extra is not None:
+                row[extra] = 1
+                if row.all():
+                    return None
+            if len(cache) >= bound:
+                cache.pop(next(iter(cache)))
+            hit = cache[key] = self._selection_tables(row, pinned=extra is None)
         return hit
 
     def _lo4_act(self, rows: int, width: int, heads: Optional[tuple] = None, sel: Optional[tuple] = None):
@@ -713,7 +766,7 @@ class LeopardEngine:
         from .ops import Lo4Act, lo4_head_k4
         return Lo4Act.empty(rows, width, self.dtype, self.device, k4=lo4_head_k4(*heads) if heads else None, sel=sel)
 
-    def _vit_layers_lo4(self, x: torch.Tensor, n: int, flags: Optional[Sequence[bool]] = None) -> torch.Tensor:
+    def _vit_layers_lo4(self, x: torch.Tensor, n: int, flags: Optional[Sequence[bool]] = None) -> None:
         """The SigLIP layers with the low-bit correction phase: the LayerNorms and fc1's GELU epilogue hand over T(y) + the fp4 image of
         y - T(y) directly, and so does the attention kernel (lmi_attn_varlen_fwd_lo4: every head padded to 96 slots in the image, out_proj's
         weight image laid out to match).  q / k / v and the attention arithmetic stay 16-bit."""
@@ -727,12 +780,7 @@ class LeopardEngine:
             key = ("vit", tuple(bool(f) for f in flags))
             sel = self._lo4_sel_cache.get(key)
             if sel is None:
-                row = np.repeat(np.array(flags, dtype=np.uint8), T)
-                unit = np.zeros((M + 63) // 64 * 64, dtype=np.uint8)
-                unit[:M] = row
-                r = np.flatnonzero(np.diff(np.concatenate([[0], row.astype(np.int8), [0]])))
-                sel = self._lo4_sel_cache[key] = (self._pinned_to_device(torch.from_numpy(row)), self._pinned_to_device(torch.from_numpy(unit.reshape(-1, 64).max(axis=1))),
-                                                  np.ascontiguousarray(r.reshape(-1, 2).astype(np.int32)))
+                sel = self._lo4_sel_cache[key] = self._selection_tables(np.repeat(np.array(flags, dtype=np.uint8), T), pinned=True)
         h, att, ff = self._lo4_act(M, D, sel=sel), self._lo4_act(M, D, heads=(H, hd), sel=sel), self._lo4_act(M, W.vit_ff, sel=sel)
         qkv = self._empty(M, W.vit_layers[0].qkv_w.shape[0])
         cu = self._vit_cu_cache[n]
@@ -747,9 +795,6 @@ class LeopardEngine:
             ops.gemm_lo4(ff, L.fc2_w, fc24, x, bias=L.fc2_b, epilogue=_lib.EPI_RESIDUAL)
             if self.trace:
                 self.trace(f"vit.{li}", x)
-        out = self._empty(M, D)
-        ops.layernorm(x, W.post_ln_w, W.post_ln_b, out, vc.layer_norm_eps)
-        return out
 
     def _llm_layers_lo4(self, x, cache, cu, cos, sin, max_len, seq_lens=None, all_rows=False, extra_rows=None):
         """The Llama / Mistral layers with the low-bit correction phase, on the FUSED schedule of the fast path: the RMSNorms ride in the GEMM
@@ -812,6 +857,35 @@ class LeopardEngine:
         ops.gemm(h1, W.proj2_w, vis, bias=W.proj2_b, epilogue=_lib.EPI_STORE_F32)
         return vis
 
+    def _warm_up(self, body, restore: Sequence[torch.Tensor] = ()) -> List[torch.Tensor]:
+        """First half of a graph capture: ``body`` runs once outside capture (first-use attribute calls, allocator) on a side stream that
+        waits on the current one, then the device counters ``restore`` get their values back.  Returns those values for ``_capture``."""
+        keep = [t.clone() for t in restore]
+        cur = torch.cuda.current_stream(self.device)
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            body()
+        cur.wait_stream(side)
+        for t, v in zip(restore, keep):
+            t.copy_(v)
+        return keep
+
+    def _capture(self, body, restore: Sequence[torch.Tensor] = (), keep: Sequence[torch.Tensor] = ()):
+        """Second half: ``body`` captured into a HIP graph; ``restore`` is put back to ``keep`` afterwards as well (capture does not execute).
+        Returns (graph, what the captured call of the body returned).  ``body`` is called as given, so a caller that wants a method looked
+        up when the step runs passes a lambda."""
+        g = torch.cuda.CUDAGraph()
+        with _capture_safe(), torch.cuda.graph(g):
+            out = body()
+        for t, v in zip(restore, keep):
+            t.copy_(v)
+        return g, out
+
+    def _capture_graph(self, body, restore: Sequence[torch.Tensor] = ()):
+        """Warm up and capture ``body`` (two calls of it), leaving the device tensors ``restore`` as they were."""
+        return self._capture(body, restore, self._warm_up(body, restore))
+
     def encode_images(self, tiles: torch.Tensor, lo4_tiles: Optional[Sequence[bool]] = None) -> torch.Tensor:
         if self.graph_encode and self.device.type == "cuda" and not self.ops.emulated and tiles.dtype == torch.uint8:
             return self._encode_images_graph(tiles, lo4_tiles)
@@ -831,16 +905,9 @@ class LeopardEngine:
         if ent is None:
             static_in = torch.empty_like(tiles)
             static_in.copy_(tiles)
-            side = torch.cuda.Stream(device=self.device)                       # warm-up outside capture (LDS attributes, allocator)
-            side.wait_stream(torch.cuda.current_stream(self.device))
             self._private_scratch = True                                       # the graph owns its tower scratch (see _carve)
             try:
-                with torch.cuda.stream(side):
-                    self.project(self.vision_tower(static_in, lo4_tiles), n)
-                torch.cuda.current_stream(self.device).wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                with _capture_safe(), torch.cuda.graph(g):
-                    static_out = self.project(self.vision_tower(static_in, lo4_tiles), n)
+                g, static_out = self._capture_graph(lambda: self.project(self.vision_tower(static_in, lo4_tiles), n))
             finally:
                 self._private_scratch = False
             if len(self._encode_graphs) >= 8:                                  # a handful of distinct N per workload; bound the pools
@@ -878,10 +945,7 @@ class LeopardEngine:
         """x: fp32 [sum(seq_lens), D] residual stream (updated in place).  Returns (logits_last [n_seq, V],
         logits_all or None).  ``cache`` (single sequence only) receives rotated K and V.  ``score_rows`` (score / score_batch): the packed
         rows whose logits are read — the lo4 schedule corrects them as well — and no head runs here: returns (None, None)."""
-        ops, W, tc = self.ops, self.W, self.cfg.text_config
-        S, D = x.shape
-        (H, KV), hd = self._llm_heads(), tc.head_dim
-        qw, kw = H * hd, KV * hd
+        S = x.shape[0]
         cu, cos, sin, last_rows, cu_list = self.sequence_geometry(seq_lens)
         assert cu_list[-1] == S
         self.llm_packed                                   # raises when a packed weight was replaced by a copy without its layout mark
@@ -891,16 +955,25 @@ class LeopardEngine:
         self.last_lo4_ranges = None
         if self.trace:
             self.trace("llm.embed", x)
-        if self.fp8 is not None or ((self.split_operands or self.lo4) and self.tp_size == 1):
-            if self.fp8 is not None:
-                self._llm_layers_fp8(x, cache, cu, cos, sin, max_len, seq_lens)
-            elif self.lo4:
-                self._llm_layers_lo4(x, cache, cu, cos, sin, max_len, seq_lens, all_rows=all_logits, extra_rows=score_rows)
-            else:
-                self._llm_layers_split(x, cache, cu, cos, sin, max_len)
-            if cache is not None:
-                cache.length = S
-            return (None, None) if score_rows is not None else self._lm_head(x, last_rows, all_logits)
+        if self.fp8 is not None:
+            self._llm_layers_fp8(x, cache, cu, cos, sin, max_len, seq_lens)
+        elif self.lo4 and self.tp_size == 1:
+            self._llm_layers_lo4(x, cache, cu, cos, sin, max_len, seq_lens, all_rows=all_logits, extra_rows=score_rows)
+        elif self.split_operands and self.tp_size == 1:
+            self._llm_layers_split(x, cache, cu, cos, sin, max_len)
+        else:
+            self._llm_layers_fast(x, cache, cu, cos, sin, max_len)
+        if cache is not None:
+            cache.length = S
+        return (None, None) if score_rows is not None else self._lm_head(x, last_rows, all_logits)
+
+    def _llm_layers_fast(self, x, cache, cu, cos, sin, max_len):
+        """The Llama / Mistral layers of the fast schedule, on the caller-owned workspace: fused (the norms and the RoPE ride in the GEMM
+        epilogues) where the shapes allow it, launch by launch otherwise (also the tensor-parallel packed prefill and the calibration pass)."""
+        ops, W, tc = self.ops, self.W, self.cfg.text_config
+        S, D = x.shape
+        (H, KV), hd = self._llm_heads(), tc.head_dim
+        qw, kw = H * hd, KV * hd
         parts = (D + 63) // 64
         total, offs = ops.llm_prefill_workspace(S, D, H, KV, hd, W.llm_ff, self.dtype)
         h, qkv, att, gu, sq_a, sq_b = self._carve("llm", total, offs, [(S, D, self.dtype), (S, qw + 2 * kw, self.dtype), (S, qw, self.dtype),
@@ -955,9 +1028,6 @@ class LeopardEngine:
                 self._row_parallel(gu, L.down_w, x, tmp)
                 if self.trace:
                     self.trace(f"llm.{i}", x)
-        if cache is not None:
-            cache.length = S
-        return (None, None) if score_rows is not None else self._lm_head(x, last_rows, all_logits)
 
     def _llm_layers_fp8(self, x, cache, cu, cos, sin, max_len, seq_lens=None):
         """The Llama layers with fp8 linears (leopard_amd.fp8): RMSNorm -> fp8 operand in one launch, the SwiGLU epilogue of
@@ -1034,6 +1104,13 @@ class LeopardEngine:
     # ------------------------------------------------------------------------------------------------
     # the whole prefill for one sample (EVAL:261-333)
     # ------------------------------------------------------------------------------------------------
+    def merged_len(self, input_ids: torch.Tensor, n_img: Optional[int] = None) -> int:
+        """Rows of a prompt's merged sequence: every image token stands for ``tokens_per_tile`` rows.  ``n_img``: the number of image tokens
+        where the caller knows it (its ViT-input count); counted from the ids otherwise."""
+        if n_img is None:
+            n_img = int((input_ids == self.cfg.image_token_index).sum())
+        return input_ids.numel() + n_img * (self.cfg.tokens_per_tile - 1)
+
     @torch.no_grad()
     def prefill(self, input_ids: torch.Tensor, tiles: Optional[torch.Tensor], cache: Optional[KVCache] = None,
                 all_logits: bool = False, keep_parts: bool = False, visual_tokens: Optional[torch.Tensor] = None
@@ -1046,7 +1123,7 @@ class LeopardEngine:
         n_tiles = 0
         if visual_tokens is None and tiles is not None and tiles.shape[0] > 0:
             n_tiles = tiles.shape[0]
-            vflags = self.lo4_vit_tiles([n_tiles], [input_ids.numel() + n_tiles * (self.cfg.tokens_per_tile - 1)])
+            vflags = self.lo4_vit_tiles([n_tiles], [self.merged_len(input_ids, n_tiles)])
             if keep_parts:
                 vit = self.vision_tower(tiles, vflags)
                 visual_tokens = self.project(vit, n_tiles)
@@ -1271,23 +1348,7 @@ class LeopardEngine:
         (``cu_seqlens`` keeps the samples apart).  samples: [(input_ids [1, S_in], tiles u8 [N_i, S, S, 3] or None)].
         Returns (logits_last [n_samples, vocab], seq_lens).  The reference runs one sample per ``generate`` call
         (EVAL:448-454); results are identical to per-sample ``prefill`` calls."""
-        tiles = [t for _, t in samples if t is not None and t.shape[0] > 0]
-        visual = None
-        if tiles:
-            all_tiles = torch.cat(tiles, dim=0)
-            with_tiles = [(ids, t) for ids, t in samples if t is not None and t.shape[0] > 0]
-            vflags = self.lo4_vit_tiles([t.shape[0] for _, t in with_tiles],
-                                        [ids.numel() + t.shape[0] * (self.cfg.tokens_per_tile - 1) for ids, t in with_tiles])
-            visual = self.encode_images(all_tiles, vflags)         # the graph-captured encode when `graph_encode` is set
-        xs, seq_lens, row = [], [], 0
-        for ids, t in samples:
-            n = 0 if t is None else t.shape[0]
-            vt = None if n == 0 else visual[row * self.cfg.tokens_per_tile:(row + n) * self.cfg.tokens_per_tile]
-            row += n
-            x = self.embed_merge(ids, vt)
-            xs.append(x)
-            seq_lens.append(x.shape[0])
-        x = torch.cat(xs, dim=0)
+        x, seq_lens = self._pack_requests(samples)
         last, _ = self.llm_prefill(x, seq_lens)
         return last, seq_lens
 
@@ -1330,13 +1391,13 @@ class LeopardEngine:
         return rows, tgt[rows], len(merged)
 
     def _request_visual(self, samples) -> List[Optional[torch.Tensor]]:
-        """Visual tokens of every (input_ids, tiles[, visual_tokens]) request: the tiles of all requests through ONE vision encode, as
-        prefill_batch does."""
+        """Visual tokens of every (input_ids, tiles[, visual_tokens]) request: the tiles of all requests through ONE vision encode (the
+        graph-captured one when ``graph_encode`` is set)."""
         tpt = self.cfg.tokens_per_tile
         need = [(s[0], s[1]) for s in samples if (len(s) < 3 or s[2] is None) and s[1] is not None and s[1].shape[0] > 0]
         visual = None
         if need:
-            vflags = self.lo4_vit_tiles([t.shape[0] for _, t in need], [ids.numel() + t.shape[0] * (tpt - 1) for ids, t in need])
+            vflags = self.lo4_vit_tiles([t.shape[0] for _, t in need], [self.merged_len(ids, t.shape[0]) for ids, t in need])
             visual = self.encode_images(torch.cat([t for _, t in need], dim=0), vflags)
         out, row = [], 0
         for s in samples:
@@ -1349,6 +1410,18 @@ class LeopardEngine:
             else:
                 out.append(None)
         return out
+
+    def _pack_requests(self, samples) -> Tuple[torch.Tensor, List[int]]:
+        """(input_ids, tiles[, visual_tokens]) requests -> (fp32 residual stream of their merged sequences, packed [sum(seq_lens), D],
+        seq_lens): all ViT inputs go through the tower and the projector together (_request_visual), ``cu_seqlens`` keeps the sequences
+        apart in the LLM pass."""
+        xs = [self.embed_merge(s[0], v) for s, v in zip(samples, self._request_visual(samples))]
+        return (torch.cat(xs, dim=0) if len(xs) > 1 else xs[0]), [x.shape[0] for x in xs]
+
+    def _move_kv(self, src: KVCache, begin: int, S: int, k_dst: List[torch.Tensor], v_dst: List[torch.Tensor], row0: int) -> None:
+        """Rows [begin, begin + S) of every layer of ``src`` -> rows [row0, row0 + S) of the per-layer caches ``k_dst`` / ``v_dst``."""
+        for i in range(len(src.k)):
+            self.ops.kv_append(src.k[i][begin:begin + S], src.v[i][begin:begin + S], k_dst[i], v_dst[i], row0)
 
     def _score_head(self, x: torch.Tensor, rows: torch.Tensor, targets: torch.Tensor):
         """Final RMSNorm of the gathered rows (lmi_rmsnorm_rows: the bits lmi_rmsnorm gives them) -> head GEMM into ONE reusable fp32 chunk of
@@ -1384,15 +1457,12 @@ class LeopardEngine:
         plans = [self.score_targets(r[0], r[2]) for r in requests]
         if not any(len(p[0]) for p in plans):                        # nothing labelled: nothing to compute (nn.CrossEntropyLoss gives nan)
             return [self._empty_score(S) for _, _, S in plans]
-        vis = self._request_visual([(r[0], r[1], None if visual_tokens is None else visual_tokens[i]) for i, r in enumerate(requests)])
-        xs = [self.embed_merge(r[0], v) for r, v in zip(requests, vis)]
-        seq_lens = [x.shape[0] for x in xs]
+        x, seq_lens = self._pack_requests([(r[0], r[1], None if visual_tokens is None else visual_tokens[i]) for i, r in enumerate(requests)])
         for (_, _, S), l in zip(plans, seq_lens):
             assert S == l
         offs = np.cumsum([0] + seq_lens[:-1])
         rows_all = np.concatenate([p[0] + o for p, o in zip(plans, offs)])
         tgt_all = np.concatenate([p[1] for p in plans])
-        x = torch.cat(xs, dim=0) if len(xs) > 1 else xs[0]
         self.llm_prefill(x, seq_lens, score_rows=rows_all)
         rows_dev = torch.from_numpy(rows_all).to(self.device)
         tgt_dev = torch.from_numpy(tgt_all).to(self.device)
@@ -1429,38 +1499,35 @@ class LeopardEngine:
     # HIP graph over static buffers; the token id and the position live in device memory (lmi_rope_qk_at, device
     # cu_seqlens), the graph itself takes the argmax and advances the position, and the host only reads the new token.
     # ------------------------------------------------------------------------------------------------
-    def _decode_state(self, cache: KVCache):
-        st = getattr(cache, "_decode_state", None)
-        if st is not None and getattr(st, "mode", None) == (self.precision, self.decode_precision):
-            return st                                                 # (a state built under another precision mode is rebuilt: other buffers, other launches)
-        W, tc = self.W, self.cfg.text_config
+    def _decode_buffers(self, B: int, capacity: int) -> DecodeState:
+        """What the batch-1 and the pooled decode state allocate alike: a function of (B, capacity) under the engine's current mode."""
+        W, tc, dev = self.W, self.cfg.text_config, self.device
         (H, KV), hd, D = self._llm_heads(), tc.head_dim, tc.hidden_size
-        dev = self.device
+        hl = self.decode_hl(B)
+        R = 2 * B if hl else B
+        cos, sin = self.rope_tables(torch.arange(capacity))
+        return DecodeState(
+            B=B, capacity=capacity, mode=(self.precision, self.decode_precision), layout=self.llm_packed, hl=hl,
+            tok=torch.zeros(B, dtype=torch.int64, device=dev), src=torch.arange(B, dtype=torch.int64, device=dev),
+            pos=torch.zeros(B, dtype=torch.int32, device=dev), cu_q=torch.arange(B + 1, dtype=torch.int32, device=dev),
+            k_begin=(torch.arange(B, dtype=torch.int32) * capacity).to(dev),
+            x=self._empty(B, D, dtype=torch.float32), h=self._empty(R, D), qkv=self._empty(B, (H + 2 * KV) * hd), att=self._empty(R, H * hd),
+            gu=self._empty(R, W.llm_ff), hf32=self._empty(B, D, dtype=torch.float32) if hl else None, cos=cos, sin=sin,
+            ws=torch.empty(self.ops.decode_workspace_elems(B, H, hd, capacity), dtype=torch.float32, device=dev),
+            temp=torch.ones(B, dtype=torch.float32, device=dev), topk=torch.zeros(B, dtype=torch.int32, device=dev),
+            topp=torch.ones(B, dtype=torch.float32, device=dev), seed=torch.zeros(B, dtype=torch.int64, device=dev),
+            step=torch.zeros(B, dtype=torch.int32, device=dev))
 
-        class St:
-            pass
-        st = St()
-        st.tok = torch.zeros(1, dtype=torch.int64, device=dev)
-        st.src0 = torch.zeros(1, dtype=torch.int64, device=dev)
-        st.pos = torch.zeros(1, dtype=torch.int32, device=dev)
-        st.cu_q = torch.tensor([0, 1], dtype=torch.int32, device=dev)
+    def _decode_state(self, cache: KVCache) -> DecodeState:
+        st = cache._decode_state
+        if st is not None and st.mode == (self.precision, self.decode_precision):
+            return st                                                 # (a state built under another precision mode is rebuilt: other buffers, other launches)
+        D, dev = self.cfg.text_config.hidden_size, self.device
+        st = self._decode_buffers(1, cache.capacity)
         st.cu_k = torch.tensor([0, 1], dtype=torch.int32, device=dev)
-        st.x = self._empty(1, D, dtype=torch.float32)
-        st.hl = self.decode_hl(1)                                     # operand buffers hold [hi row; lo row] pairs (decode precision mode)
-        R = 2 if st.hl else 1
-        st.h, st.qkv, st.att = self._empty(R, D), self._empty(1, (H + 2 * KV) * hd), self._empty(R, H * hd)
-        st.gu = self._empty(R, W.llm_ff)
-        st.hf32 = self._empty(1, D, dtype=torch.float32) if st.hl else None
-        st.part = torch.zeros(D, dtype=torch.float32, device=dev)     # tensor parallel: partial o_proj / down_proj row
+        st.part = torch.zeros(D, dtype=torch.float32, device=dev)
         st.sq_a, st.sq_b = self._empty(1, max(D // 16, 1), dtype=torch.float32), self._empty(1, max(D // 16, 1), dtype=torch.float32)
-        st.k_begin = torch.zeros(1, dtype=torch.int32, device=dev)    # packed weights: the step runs on the batched-decode kernels with one row
-        st.logits = self._empty(W.lm_head.shape[0], dtype=torch.float32)
-        st.cos, st.sin = self.rope_tables(torch.arange(cache.capacity))
-        st.ws = torch.empty(self.ops.decode_workspace_elems(1, H, hd, cache.capacity), dtype=torch.float32, device=dev)
-        st.graph = None
-        self._sampling_buffers(st, 1)
-        st.layout = self.llm_packed                                   # a captured step replays the launches of the weight layout it was captured on
-        st.mode = (self.precision, self.decode_precision)             # ... and of the precision mode
+        st.logits = self._empty(self.W.lm_head.shape[0], dtype=torch.float32)
         cache._decode_state = st
         return st
 
@@ -1478,7 +1545,7 @@ class LeopardEngine:
             ops.gemv(w, a, st.part, epilogue=0)
             self.comm.all_reduce(st.part)
             st.x[0].add_(st.part)
-        ops.embed_merge(st.tok, st.src0, W.embed, None, st.x)
+        ops.embed_merge(st.tok, st.src, W.embed, None, st.x)
         if self.llm_packed:
             # one copy of the weights, in the operand order of lmi_gemm_skinny: the batch-1 step is the batched step with one row (measured:
             # 3.10 ms per step at B = 2 against 3.12 ms for the GEMV step), its KV rows go to this cache, the head keeps the fp32 row
@@ -1513,18 +1580,6 @@ class LeopardEngine:
         # greedy (or sampled) choice and position / key-count advance stay on the device, one launch (lmi_decode_advance /
         # lmi_decode_sample; capturable)
         self._choose(st, st.logits.view(1, -1), k_len=st.cu_k[1:])
-
-    def _sampling_buffers(self, st, B: int) -> None:
-        """Per-row sampling parameters of a decode state, in device memory: written before a replay, read by the captured step, so new
-        parameters never need a new capture.  ``st.sampling`` selects which of the two captured steps runs (``graph`` / ``graph_s``)."""
-        dev = self.device
-        st.sampling = False
-        st.graph_s = None
-        st.temp = torch.ones(B, dtype=torch.float32, device=dev)
-        st.topk = torch.zeros(B, dtype=torch.int32, device=dev)
-        st.topp = torch.ones(B, dtype=torch.float32, device=dev)
-        st.seed = torch.zeros(B, dtype=torch.int64, device=dev)
-        st.step = torch.zeros(B, dtype=torch.int32, device=dev)
 
     def _set_sampling(self, st, j: int, sp: "SamplingParams", step: int = 1) -> None:
         """Row j of a decode state draws with ``sp`` from counter ``step`` on (the token from the prefill was step 0)."""
@@ -1565,27 +1620,20 @@ class LeopardEngine:
         # lmi_allreduce on the device), so the step stays ONE graph replay per token; over a torch.distributed group (gloo in the
         # CPU tests, host-staged) it cannot be captured and runs eagerly.
         from .dist import RcclComm
-        if getattr(st, "layout", self.llm_packed) != self.llm_packed:      # pack_llm_weights / unpack_llm_weights since the capture
+        if st.layout != self.llm_packed:                                   # pack_llm_weights / unpack_llm_weights since the capture
             st.graph, st.graph_s, st.layout = None, None, self.llm_packed
         gname = "graph_s" if st.sampling else "graph"                      # greedy and sampled steps: one captured graph each
         tp_capturable = self.tp_size == 1 or (isinstance(self.comm, RcclComm) and self.tp_decode_graph)
-        if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs or not tp_capturable or getattr(st, "graph_failed", False):
+        if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs or not tp_capturable or st.graph_failed:
             self._decode_body(st, cache)
             return
         if getattr(st, gname) is None:
-            # warm-up outside capture (first-use attribute calls, allocator), on copies of the device counters
-            keep = (st.tok.clone(), st.pos.clone(), st.cu_k.clone(), st.step.clone())
-            side = torch.cuda.Stream(device=self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                self._decode_body(st, cache)
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            st.tok.copy_(keep[0]); st.pos.copy_(keep[1]); st.cu_k.copy_(keep[2]); st.step.copy_(keep[3])
+            restore = (st.tok, st.pos, st.cu_k, st.step)
+            body = lambda: self._decode_body(st, cache)
+            keep = self._warm_up(body, restore)        # (what the warm-up sends counts in comm.sent_bytes)
             sent0 = self.comm.sent_bytes if self.comm is not None else 0
             try:
-                g = torch.cuda.CUDAGraph()
-                with _capture_safe(), torch.cuda.graph(g):
-                    self._decode_body(st, cache)
+                g, _ = self._capture(body, restore, keep)
             except Exception as exc:                   # a communicator that cannot be captured: run the step eagerly from now on
                 if self.tp_size == 1:
                     raise
@@ -1593,17 +1641,17 @@ class LeopardEngine:
                 warnings.warn(f"tensor-parallel decode step could not be captured in a HIP graph ({exc}); running it eagerly")
                 st.graph_failed = True
                 torch.cuda.synchronize(self.device)
-                st.tok.copy_(keep[0]); st.pos.copy_(keep[1]); st.cu_k.copy_(keep[2]); st.step.copy_(keep[3])
+                for t, v in zip(restore, keep):
+                    t.copy_(v)
                 self._decode_body(st, cache)
                 return
             st.graph_comm_bytes = (self.comm.sent_bytes - sent0) if self.comm is not None else 0    # what one replay puts on the links
             if self.comm is not None:
                 self.comm.sent_bytes = sent0           # capture records, it does not send
-            st.tok.copy_(keep[0]); st.pos.copy_(keep[1]); st.cu_k.copy_(keep[2]); st.step.copy_(keep[3])      # capture does not execute
             setattr(st, gname, g)
         getattr(st, gname).replay()
         if self.comm is not None:
-            self.comm.sent_bytes += getattr(st, "graph_comm_bytes", 0)
+            self.comm.sent_bytes += st.graph_comm_bytes
 
     def _decode_seed(self, st, cache: KVCache, token_id: int):
         if cache.length >= cache.capacity:
@@ -1627,7 +1675,7 @@ class LeopardEngine:
         batch 1 with at most 128 new tokens, and a fresh cache per sample would pay an eager warm-up step, a graph capture and new
         static buffers every time.  The graph reads the position and the key count from device memory and its launch geometry
         depends only on the capacity, so resetting ``length`` is all a new prompt needs; a longer prompt grows the cache."""
-        c = getattr(self, "_gen_cache", None)
+        c = self._gen_cache
         if c is None or c.capacity < need:
             c = self._gen_cache = KVCache(self.cfg, (need + 2047) // 2048 * 2048, self.dtype, self.device, tp_size=self.tp_size)
         c.length = 0
@@ -1664,8 +1712,7 @@ class LeopardEngine:
                  eos_token_id: Sequence[int] = (128001, 128009), sampling: Optional[SamplingParams] = None) -> torch.Tensor:
         """Greedy generation (EVAL:448-452), or sampled with ``sampling``: returns LongTensor [1, S_in + T] on the input device."""
         ids = input_ids.reshape(1, -1)
-        n_img = int((ids == self.cfg.image_token_index).sum())
-        S = ids.shape[1] + n_img * (self.cfg.tokens_per_tile - 1)
+        S = self.merged_len(ids)
         cache = self._generation_cache((self.tp_padded_len(S) if self.tp_size > 1 else S) + max_new_tokens)
         res = self.prefill(ids, tiles, cache=cache)
         first = self.first_token(res.logits_last) if sampling is None else self.sample_first(res.logits_last, [sampling])[0]
@@ -1689,43 +1736,23 @@ class LeopardEngine:
         return (hd == 128 and D % 128 == 0 and W.llm_ff % 128 == 0 and (2 * W.llm_ff) % 64 == 0 and ((H + 2 * KV) * hd) % 16 == 0 and
                 W.lm_head.shape[0] % 16 == 0 and D % 16 == 0)
 
-    def _batch_state(self, B: int, need: int):
+    def _batch_state(self, B: int, need: int) -> DecodeState:
         """Static buffers + pooled KV cache + captured graph of a B-sequence decode step (kept per engine and reused: the graph reads
         positions / key counts from device memory and its launch geometry depends on (B, capacity) only)."""
-        states = getattr(self, "_batch_states", None)
-        if states is None:
-            states = self._batch_states = {}
+        states = self._batch_states
         st = states.get(B)
-        if st is not None and st.capacity >= need and getattr(st, "mode", None) == (self.precision, self.decode_precision):
+        if st is not None and st.capacity >= need and st.mode == (self.precision, self.decode_precision):
             return st
         W, tc, dev = self.W, self.cfg.text_config, self.device
         (H, KV), hd, D = self._llm_heads(), tc.head_dim, tc.hidden_size
         cap = (need + 1023) // 1024 * 1024
-
-        class St:
-            pass
-        st = St()
-        st.B, st.capacity = B, cap
+        st = self._decode_buffers(B, cap)
         n_layers = len(W.llm_layers)
         st.k = [torch.zeros(B * cap, KV * hd, dtype=self.dtype, device=dev) for _ in range(n_layers)]
         st.v = [torch.zeros(B * cap, KV * hd, dtype=self.dtype, device=dev) for _ in range(n_layers)]
-        st.tok = torch.zeros(B, dtype=torch.int64, device=dev)
-        st.src = torch.arange(B, dtype=torch.int64, device=dev)
-        st.pos = torch.zeros(B, dtype=torch.int32, device=dev)
         st.k_len = torch.ones(B, dtype=torch.int32, device=dev)
-        st.k_begin = (torch.arange(B, dtype=torch.int32) * cap).to(dev)
-        st.cu_q = torch.arange(B + 1, dtype=torch.int32, device=dev)
-        st.x = self._empty(B, D, dtype=torch.float32)
-        st.hl = self.decode_hl(B)                                     # [hi rows; lo rows] operand pairs (decode precision mode; 2 B <= 16)
-        R = 2 * B if st.hl else B
-        st.h, st.qkv, st.att = self._empty(R, D), self._empty(B, (H + 2 * KV) * hd), self._empty(R, H * hd)
-        st.gu = self._empty(R, W.llm_ff)
-        st.hf32 = self._empty(B, D, dtype=torch.float32) if st.hl else None
-        st.mode = (self.precision, self.decode_precision)
         st.sq_a, st.sq_b = self._empty(B, D // 16, dtype=torch.float32), self._empty(B, D // 16, dtype=torch.float32)   # folded-norm partials
         st.logits = self._empty(B, W.lm_head.shape[0], dtype=torch.float32)
-        st.cos, st.sin = self.rope_tables(torch.arange(cap))
-        st.ws = torch.empty(self.ops.decode_workspace_elems(B, H, hd, cap), dtype=torch.float32, device=dev)
         # continuous batching (generate_stream): which slots hold a running sequence, how many more tokens each may produce, the eos ids,
         # and a ring of the last HIST steps' tokens — all in device memory, so that slots are admitted / retired between replays of ONE
         # captured step and the host looks at the tokens only every HIST steps
@@ -1734,8 +1761,6 @@ class LeopardEngine:
         st.eos = torch.full((self.MAX_EOS,), -1, dtype=torch.int64, device=dev)
         st.hist = torch.zeros(self.HIST, B, dtype=torch.int64, device=dev)
         st.hist_pos = torch.zeros(B, dtype=torch.int32, device=dev)
-        st.graph = None
-        self._sampling_buffers(st, B)
         # bounded: a serving process that sees many batch sizes keeps the pools of the two most recent ones (each is B x capacity KV rows)
         while len(states) >= 2:
             states.pop(next(iter(states)))
@@ -1746,7 +1771,7 @@ class LeopardEngine:
         """The decode projections + the head in lmi_gemm_skinny's packed (MFMA operand) order — a second copy of the 16-bit LLM weights
         (15 GB for Llama-3.1-8B), built on the first batched decode and shared by every batch size.  Only engines whose weights stay in
         the nn.Linear layout (tensor parallel, pack_llm_weights=False) need it: the default layout IS this order (pack_llm_weights)."""
-        pk = getattr(self, "_skinny_pack", None)
+        pk = self._skinny_pack
         if pk is None:
             from .weights import skinny_pack
             W = self.W
@@ -1768,7 +1793,7 @@ class LeopardEngine:
         # per-row partial sums of squares, the projection that consumes them scales its accumulator rows by rstd — only the first
         # layer's norm and the final one stay launches of their own
         fold = self.skinny_fold_norm and D % 16 == 0 and all(L.qkv_w_rope is not None for L in W.llm_layers) and hd == 128
-        hl = bool(getattr(st, "hl", False))                           # decode precision mode: operands are [hi rows; lo rows] pairs (decode_hl)
+        hl = st.hl                                                    # decode precision mode: operands are [hi rows; lo rows] pairs (decode_hl)
         assert not hl or fold
         for i, L in enumerate(W.llm_layers):
             rope_fused = L.qkv_w_rope is not None and hd == 128
@@ -1801,10 +1826,10 @@ class LeopardEngine:
 
     def _skinny_head(self):
         """lm_head in the packed order for the batched step (shared with _skinny_weights' second copy when there is one)."""
-        h = getattr(self, "_head_pack", None)
+        h = self._head_pack
         if h is None:
             from .weights import as_packed
-            pk = getattr(self, "_skinny_pack", None)
+            pk = self._skinny_pack
             h = self._head_pack = as_packed(pk["head"]) if pk else as_packed(self.W.lm_head)
         return h
 
@@ -1837,20 +1862,8 @@ class LeopardEngine:
             return
         gname = "graph_s" if st.sampling else "graph"                      # greedy and sampled steps: one captured graph each
         if getattr(st, gname) is None:
-            names = ("tok", "pos", "k_len", "live", "budget", "hist", "hist_pos", "step")
-            keep = [getattr(st, n).clone() for n in names]
-            side = torch.cuda.Stream(device=self.device)               # warm-up outside capture (function attributes, allocator)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                self._batch_decode_body(st)
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            for n, v in zip(names, keep):
-                getattr(st, n).copy_(v)
-            g = torch.cuda.CUDAGraph()
-            with _capture_safe(), torch.cuda.graph(g):
-                self._batch_decode_body(st)
-            for n, v in zip(names, keep):                              # capture does not execute
-                getattr(st, n).copy_(v)
+            g, _ = self._capture_graph(lambda: self._batch_decode_body(st),
+                                       (st.tok, st.pos, st.k_len, st.live, st.budget, st.hist, st.hist_pos, st.step))
             setattr(st, gname, g)
         getattr(st, gname).replay()
 
@@ -1912,10 +1925,7 @@ class LeopardEngine:
         req = (lambda i: None) if sampling is None else sampling.for_request
         if B == 1 or not self._batch_decode_supported() or len(eos) > self.MAX_EOS:
             return [self.generate(ids, t() if callable(t) else t, max_new_tokens, eos, sampling=req(i)) for i, (ids, t) in enumerate(samples)]
-        tpt = self.cfg.tokens_per_tile
-        def merged_len(ids):
-            return ids.shape[-1] + int((ids == self.cfg.image_token_index).sum()) * (tpt - 1)
-        need = max(merged_len(ids) for ids, _ in samples) + max_new_tokens
+        need = max(self.merged_len(ids) for ids, _ in samples) + max_new_tokens
         st = self._batch_state(B, need)
         st.eos.fill_(-1)
         if eos:
@@ -1928,7 +1938,7 @@ class LeopardEngine:
         h_budget = [0] * B                                           # host mirror of the device stop rule
         pending = list(range(len(samples)))
         n_steps = slot_steps = live_steps = 0
-        scratch = getattr(self, "_stream_cache", None)
+        scratch = self._stream_cache
 
         def admit(j: int) -> bool:
             """Next pending sample into slot j; False when nothing is pending.  Samples that end with their first token never take a slot."""
@@ -1938,7 +1948,7 @@ class LeopardEngine:
                 ids, tiles = samples[i]
                 if callable(tiles):                                   # lazy pixels: prepared when the sample is admitted, dropped after its prefill
                     tiles = tiles()
-                S = merged_len(ids)
+                S = self.merged_len(ids)
                 if scratch is None or scratch.capacity < S:
                     scratch = self._stream_cache = KVCache(self.cfg, (S + 1023) // 1024 * 1024, self.dtype, self.device)
                 scratch.length = 0
@@ -1948,8 +1958,7 @@ class LeopardEngine:
                 outs[i] = out
                 if first in eos_set or max_new_tokens <= 1:
                     continue                                          # finished by the prefill alone
-                for li in range(len(scratch.k)):
-                    self.ops.kv_append(scratch.k[li][:S], scratch.v[li][:S], st.k[li], st.v[li], j * st.capacity)
+                self._move_kv(scratch, 0, S, st.k, st.v, j * st.capacity)
                 dev = self.device
                 st.tok[j:j + 1].copy_(torch.tensor([first], dtype=torch.int64, device=dev))
                 st.pos[j:j + 1].copy_(torch.tensor([S], dtype=torch.int32, device=dev))
@@ -2013,23 +2022,9 @@ class LeopardEngine:
         if len(samples) == 1:
             ids, t = samples[0]
             return [self.generate(ids, t, max_new_tokens, eos_token_id, sampling=req(0))]
-        tiles = [t for _, t in samples if t is not None and t.shape[0] > 0]
-        visual = None
-        if tiles:
-            all_tiles = torch.cat(tiles, dim=0)
-            with_tiles = [(ids, t) for ids, t in samples if t is not None and t.shape[0] > 0]
-            visual = self.encode_images(all_tiles, self.lo4_vit_tiles([t.shape[0] for _, t in with_tiles],
-                                                                      [ids.numel() + t.shape[0] * (self.cfg.tokens_per_tile - 1) for ids, t in with_tiles]))
-        xs, seq_lens, row = [], [], 0
-        for ids, t in samples:
-            n = 0 if t is None else t.shape[0]
-            vt = None if n == 0 else visual[row * self.cfg.tokens_per_tile:(row + n) * self.cfg.tokens_per_tile]
-            row += n
-            x = self.embed_merge(ids, vt)
-            xs.append(x)
-            seq_lens.append(x.shape[0])
+        x, seq_lens = self._pack_requests(samples)
         packed = KVCache(self.cfg, sum(seq_lens), self.dtype, self.device)
-        last, _ = self.llm_prefill(torch.cat(xs, dim=0), seq_lens, cache=packed)
+        last, _ = self.llm_prefill(x, seq_lens, cache=packed)
         if sampling is None:
             first = [self.first_token(last[j]) for j in range(last.shape[0])]
         else:
@@ -2041,8 +2036,7 @@ class LeopardEngine:
             outs, off = [], 0
             for j, ((ids, _), S, nxt) in enumerate(zip(samples, seq_lens, first)):
                 cache = self._generation_cache(S + max_new_tokens)
-                for i in range(len(cache.k)):
-                    self.ops.kv_append(packed.k[i][off:off + S], packed.v[i][off:off + S], cache.k[i], cache.v[i], 0)
+                self._move_kv(packed, off, S, cache.k, cache.v, 0)
                 cache.length = S
                 off += S
                 out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], nxt, cache, max_new_tokens, eos, req(j))
@@ -2051,8 +2045,7 @@ class LeopardEngine:
         st = self._batch_state(len(samples), max(seq_lens) + max_new_tokens)
         off = 0
         for j, S in enumerate(seq_lens):
-            for i in range(len(packed.k)):
-                self.ops.kv_append(packed.k[i][off:off + S], packed.v[i][off:off + S], st.k[i], st.v[i], j * st.capacity)
+            self._move_kv(packed, off, S, st.k, st.v, j * st.capacity)
             off += S
         del packed
         prompts = [[int(t) for t in ids.reshape(-1).tolist()] for ids, _ in samples]

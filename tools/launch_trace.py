@@ -1,0 +1,174 @@
+"""Launch-trace recorder: which library entries the engine calls, in which order, with which scalar arguments — without a GPU.
+
+Every kernel goes through ``Ops.lib.<lmi_...>``.  This script wraps the emulator build of the library (``make emu``) in a recording proxy
+(entry name + every non-pointer scalar argument; a pointer is recorded as null / non-null only), drives LeopardEngine through its host
+paths on the micro configuration of tests/test_emu_engine.py (LLM width 256, which the lo4 schedule needs) and prints one SHA-256 per scenario.  Two commits whose engine issues the
+same launches print the same hashes: the check for a refactor of the host plumbing (``--dump DIR`` writes the traces themselves).
+
+    make emu && python tools/launch_trace.py
+"""
+import argparse
+import ctypes
+import hashlib
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import numpy as np   # noqa: E402
+import torch         # noqa: E402
+
+from leopard_amd import _lib                                                            # noqa: E402
+from leopard_amd.config import LeopardConfig, RopeScaling, TextConfig, VisionConfig     # noqa: E402
+from leopard_amd.engine import LeopardEngine, SamplingParams                            # noqa: E402
+from leopard_amd.ops import Ops                                                         # noqa: E402
+from leopard_amd.weights import EngineWeights, SynthSource                              # noqa: E402
+
+EMU = os.path.join(REPO, "tools", "hipemu", "libleopard_amd_emu.so")
+QUIET = ("lmi_last_error", "lmi_abi_version")        # not launches
+
+
+class Recorder:
+    """Stands in for the bound library: forwards every call, keeps (name, scalars) of each."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, []
+
+    @staticmethod
+    def _scalar(a):
+        if isinstance(a, ctypes.c_void_p):
+            return "p" if a.value else "null"
+        if isinstance(a, (bool, int, float, bytes, str)):
+            return a
+        if isinstance(a, ctypes._SimpleCData):
+            return a.value
+        return None                                   # arrays the entry fills in (workspace offsets): not an argument value
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name in QUIET:
+            return fn
+
+        def call(*args):
+            self.calls.append((name,) + tuple(s for s in map(self._scalar, args) if s is not None))
+            return fn(*args)
+        return call
+
+
+def micro_config(vit_layers=1):
+    return LeopardConfig(
+        vision_config=VisionConfig(hidden_size=1152, intermediate_size=100, num_hidden_layers=vit_layers, num_attention_heads=16,
+                                   image_size=28, patch_size=14),
+        text_config=TextConfig(hidden_size=256, intermediate_size=128, num_hidden_layers=2, num_attention_heads=2,
+                               num_key_value_heads=1, vocab_size=256, rope_scaling=RopeScaling()),
+        image_token_index=250)
+
+
+def tiles(seed, n):
+    return torch.from_numpy(np.random.default_rng(seed).integers(0, 256, (n, 28, 28, 3), dtype=np.uint8))
+
+
+def engine(ops, vit_layers=1):
+    cfg = micro_config(vit_layers)
+    W = EngineWeights.build(cfg, SynthSource(cfg, ops, "cpu", torch.float16), torch.float16)
+    return LeopardEngine(cfg, W, ops=ops, device="cpu")
+
+
+def scenarios(ops):
+    """name -> zero-argument callable: the recorded part of the scenario (engines, weights and fp8 plans are built here, outside it)."""
+    ids3 = torch.tensor([[5, 250, 9, 250, 250, 17, 33]])
+    samples = [(torch.tensor([[5, 250, 9, 250, 17]]), tiles(5, 2)), (torch.tensor([[7, 8, 9]]), None), (torch.tensor([[250, 3]]), tiles(6, 1))]
+    text_only = [(torch.tensor([[7, 8, 9]]), None), (torch.tensor([[1, 2, 3, 4]]), None)]
+    long_ids = torch.tensor([[250] + [int(v) for v in np.random.default_rng(1).integers(0, 240, 39)]])
+    sp = SamplingParams(temperature=0.8, top_k=20, top_p=0.9, seed=11)
+    out = {}
+
+    def prefill(mode):
+        eng = engine(ops)
+        eng.precision = mode
+        return lambda: eng.prefill(ids3, tiles(3, 3))
+    for mode in ("fast", "lo4", "split"):
+        out[f"prefill_{mode}"] = prefill(mode)
+
+    def prefill_unfused():
+        eng = engine(ops)
+        eng.fuse_norm_rope = False
+        return lambda: eng.prefill(ids3, tiles(3, 3), cache=None, all_logits=True)
+    out["prefill_fast_unfused_all_logits"] = prefill_unfused()
+
+    def prefill_batch(mode, smp, full_below=None):
+        eng = engine(ops)
+        eng.precision = mode
+        if full_below is not None:                    # "auto" lo4_vit: samples above this many rows keep the fast tower -> mixed ViT flags
+            eng.LO4_FULL_BELOW = full_below
+        return lambda: eng.prefill_batch(smp)
+    out["prefill_batch_fast"] = prefill_batch("fast", samples)
+    out["prefill_batch_fast_text_only"] = prefill_batch("fast", text_only)
+    out["prefill_batch_lo4"] = prefill_batch("lo4", samples)
+    out["prefill_batch_lo4_mixed_tower"] = prefill_batch("lo4", samples, full_below=4)
+
+    def score_batch(rows, n_text):
+        eng = engine(ops)
+        eng.precision = "lo4"
+        eng.lo4_rows = rows
+        ids = torch.tensor([[250] + [int(v) for v in np.random.default_rng(2).integers(0, 240, n_text)]])
+        lab = torch.full_like(ids, -100)
+        lab[0, 3:6] = ids[0, 3:6]
+        lab[0, -2:] = ids[0, -2:]
+        short = torch.tensor([[7, 8, 9, 10]])
+        reqs = [(ids, tiles(7, 1), lab), (short, None, torch.tensor([[-100, -100, 9, 10]]))]
+        return lambda: (eng.score_batch(reqs), eng.score(ids, tiles(7, 1), lab))
+    out["score_batch_lo4_tail8"] = score_batch(8, 39)
+    out["score_batch_lo4_auto_long"] = score_batch("auto", 1100)
+
+    def gen(kind, sampling):
+        eng = engine(ops)
+        if kind == "generate":
+            return lambda: eng.generate(long_ids[:, :6], tiles(4, 1), max_new_tokens=4, eos_token_id=(), sampling=sampling)
+        if kind == "generate_batch":
+            return lambda: eng.generate_batch(samples, max_new_tokens=4, eos_token_id=(), sampling=sampling)
+        return lambda: eng.generate_stream(samples + text_only, batch_size=2, max_new_tokens=11, eos_token_id=(), sampling=sampling)
+    for kind in ("generate", "generate_batch", "generate_stream"):
+        out[f"{kind}_greedy"] = gen(kind, None)
+        out[f"{kind}_sampled"] = gen(kind, sp)
+
+    def gen_lo4():
+        eng = engine(ops)
+        eng.precision = "lo4"
+        return lambda: (eng.generate(long_ids[:, :6], tiles(4, 1), max_new_tokens=3, eos_token_id=()),
+                        eng.generate_batch(samples, max_new_tokens=3, eos_token_id=()))
+    out["generate_and_batch_lo4"] = gen_lo4()
+
+    def fp8():
+        eng = engine(ops, vit_layers=2)
+        eng.enable_fp8([(torch.tensor([[3, 250, 250, 8]]), tiles(9, 2))])
+        return lambda: eng.prefill(ids3, tiles(3, 3), all_logits=True)
+    out["prefill_fp8"] = fp8()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--only", nargs="*", help="scenario names (default: all)")
+    ap.add_argument("--dump", help="directory for one text file per scenario: a call per line")
+    args = ap.parse_args()
+    if not os.path.exists(EMU):
+        sys.exit("build the emulator library first: make emu")
+    rec = Recorder(_lib.bind(EMU))
+    ops = Ops(lib=rec, emulated=True)
+    for name, run in scenarios(ops).items():
+        if args.only and name not in args.only:
+            continue
+        rec.calls = []
+        run()
+        text = "\n".join(repr(c) for c in rec.calls)
+        if args.dump:
+            os.makedirs(args.dump, exist_ok=True)
+            with open(os.path.join(args.dump, name + ".txt"), "w") as f:
+                f.write(text + "\n")
+        print(f"{name:34s} {len(rec.calls):6d} calls  sha256 {hashlib.sha256(text.encode()).hexdigest()[:16]}")
+
+
+if __name__ == "__main__":
+    main()
