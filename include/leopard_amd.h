@@ -300,6 +300,22 @@ int lmi_attn_varlen_fwd_lo4(const void* q, const void* k, const void* v, void* o
 int lmi_attn_varlen_fwd_lo4_rows(const void* q, const void* k, const void* v, void* out, void* out4, void* out4_scale, int ld_out4, int ld_out4s,
                                  const int* cu_seqlens_q, const int* cu_seqlens_k, int n_seq, int max_seqlen_q, int n_heads, int n_kv_heads, int head_dim,
                                  int ldq, int ldk, int ldv, int ldo, float scale, int causal, int window, const void* row_sel, int dtype, void* stream);
+/* Causal self-attention of n_seq packed sequences (cu_seqlens [n_seq + 1]; q / k / v rows as lmi_attn_varlen_fwd with cu_seqlens_q == cu_seqlens_k)
+ * that all continue ONE shared, already cached key range: sequence s attends to [k_prefix rows 0 .. prefix_len) ; its own rows].  Every prefix key
+ * is visible to every query row, the own range is causal (query i sees own keys j <= i).  The prefix (row strides ldkp / ldvp, kv head h at
+ * + h * head_dim, e.g. one layer of a KV cache) is read in place and never written; the same for every sequence of the launch.  Keys are walked in
+ * key order in 64-key tiles, prefix tiles first: with prefix_len % 64 == 0 the result equals, bit for bit, lmi_attn_varlen_fwd over a contiguous
+ * copy [prefix ; own] with key lengths prefix_len + len.  LDS-DMA kernel only.  LMI_EINVAL (never a trap) for: head_dim != 128, prefix_len < 1,
+ * row strides below the heads' width or not multiples of 8, (prefix + longest own range) K / V rows spanning >= 4 GiB.  No sliding window, no
+ * split-KV, no GQA packing. */
+int lmi_attn_prefix_fwd(const void* q, const void* k, const void* v, const void* k_prefix, const void* v_prefix, int prefix_len, void* out,
+                        const int* cu_seqlens, int n_seq, int max_seqlen_q, int n_heads, int n_kv_heads, int head_dim, int ldq, int ldk, int ldv,
+                        int ldkp, int ldvp, int ldo, float scale, int dtype, void* stream);
+/* the same, also writing the residual image of its 16-bit output rows as lmi_attn_varlen_fwd_lo4_rows does (row_sel [total_q] bytes, null = every row) */
+int lmi_attn_prefix_fwd_lo4_rows(const void* q, const void* k, const void* v, const void* k_prefix, const void* v_prefix, int prefix_len, void* out,
+                                 void* out4, void* out4_scale, int ld_out4, int ld_out4s, const int* cu_seqlens, int n_seq, int max_seqlen_q, int n_heads,
+                                 int n_kv_heads, int head_dim, int ldq, int ldk, int ldv, int ldkp, int ldvp, int ldo, float scale, const void* row_sel,
+                                 int dtype, void* stream);
 /* fp32 activation [M, K] (K % 32 == 0) -> hi = T(x) [M, ldh] + the fp4 image of x - T(x) [M, ld4 bytes] + its block scales [M, lds]
  * (attention outputs: lmi_attn_varlen_fwd_f32 hands over fp32). */
 int lmi_split_lo4(const float* x, void* hi, void* lo4, void* scales, int M, int K, int K4, int ldx, int ldh, int ld4, int lds, int dtype, void* stream);

@@ -136,6 +136,11 @@ class LeopardForConditionalGeneration:
         if past_key_values is not None and input_ids.shape[1] == 1:          # decode branch, EVAL:291-320
             logits = eng.decode_step(int(input_ids[0, 0]), past_key_values)
             return LlavaCausalLMOutputWithPast(logits=logits.view(1, 1, -1), past_key_values=past_key_values)
+        if past_key_values is not None and input_ids.shape[1] > 1 and labels is None:
+            # multi-turn (HF semantics: append n rows to the cache): the n new ids run against the cached rows (LeopardEngine.append);
+            # pixel_values are ignored here as in the decode branch — images belong to the call that built the cache
+            logits = eng.append(past_key_values, input_ids.to(self.device))
+            return LlavaCausalLMOutputWithPast(logits=logits.unsqueeze(0), past_key_values=past_key_values)
         if labels is not None:
             if past_key_values is not None:
                 raise NotImplementedError("labels score a whole prompt: no past_key_values")
@@ -195,6 +200,19 @@ class LeopardForConditionalGeneration:
         samples = [(ids.to(self.device), self._as_tiles(pix)) for ids, pix in requests]
         return self.engine.generate_batch(samples, max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp)
 
+
+    @torch.no_grad()
+    def generate_shared(self, prefix_ids, pixel_values, suffix_ids_list: Sequence[torch.Tensor], eos_token_id=None, max_new_tokens: int = 128,
+                        do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None, **unused) -> List[torch.Tensor]:
+        """Many questions about one set of images: ``prefix_ids`` [1, S_p] (the chat head and every image group, with ``pixel_values``) is
+        prefilled ONCE — the vision tower runs once — and the text-only ``suffix_ids_list`` ([1, s_j] each: question, instruction, tail)
+        continue from its cache together (LeopardEngine.generate_shared).  Returns [LongTensor [1, S_p + s_j + T]], each what ``generate``
+        returns for the concatenated prompt.  Decoding kwargs as ``generate_batch``; request i draws with its own seed.  Memory: every decode
+        slot holds its own copy of the prefix rows, B x (P + s + T) rows per layer."""
+        sp = self._sampling("generate_shared", unused, do_sample, temperature, top_k, top_p, seed)
+        eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
+        return self.engine.generate_shared(prefix_ids.to(self.device), self._as_tiles(pixel_values), [s.to(self.device) for s in suffix_ids_list],
+                                           max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp)
 
     @torch.no_grad()
     def generate_stream(self, requests: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8, eos_token_id=None,

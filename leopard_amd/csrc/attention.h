@@ -60,6 +60,13 @@ struct AttnArgs {
     const uint8_t* row_sel;   // [total_q] or null: the rows whose image is wanted (gemm.h GemmArgs::row_sel); the others only get their 16-bit row
     int gqa_pack;             // LDS-DMA kernel, decode: a workgroup's 4 waves take the 4 query heads of ONE kv head (32 query rows per block)
     int check_k_extent;       // 1 = the launcher could not bound a sequence's K / V extent (< 4 GiB): the kernel checks (and traps)
+    // LDS-DMA kernel, optional (the PREFIX instantiation, head_dim 128): a key range SHARED by every sequence of the launch, in front of the
+    // sequence's own keys.  Sequence s sees [prefix rows 0 .. prefix_len) ; own rows cu_k[s] .. cu_k[s + 1)] with len_k[s] == len_q[s]: every
+    // prefix key is visible to every query, the own range is causal.  The prefix is read in place (a KV cache filled once), never copied.
+    const void* k_prefix;     // head kvh at k_prefix + row*ldkp + kvh*D; null = no prefix
+    const void* v_prefix;
+    int ldkp, ldvp;
+    int prefix_len;           // P >= 1 (host integer)
 };
 
 constexpr int ATT_BQ = 128, ATT_BKV = 64, ATT_THREADS = 256;
@@ -317,8 +324,14 @@ LMI_DEV int att_vchunk72(int r4, int pos) {                    // inverse: which
     return (int)((INV[r4] >> (4 * pos)) & 15);
 }
 
-template <typename T, int D, bool CAUSAL, bool STREAM = false>      // STREAM: non-temporal K / V loads (decode: each tile is read once)
+// PREFIX (AttnArgs::k_prefix): the key walk has two ranges.  Tiles t < PT = ceil(P / 64) are the shared prefix rows, DMA'd through a second
+// pair of buffer resources (rows >= P read as zeros through the resource bound; the last prefix tile masks its columns >= P — the mask step
+// in mid-stream); tiles t >= PT are the sequence's own rows, restarting at own row 0, causal as ever.  The tiles are walked in key order, so
+// with P a multiple of 64 the partition — and every bit of the result — is that of a launch over a contiguous copy [prefix ; own].  Every
+// tile, of either range, is the same 2 * PPW pieces per wave into the same ring: the vmcnt(0) + barrier hand-over is untouched.
+template <typename T, int D, bool CAUSAL, bool STREAM = false, bool PREFIX = false>      // STREAM: non-temporal K / V loads (decode: each tile is read once)
 __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p) {
+    static_assert(!PREFIX || (CAUSAL && D == 128 && !STREAM), "the prefix range: causal self-attention at head_dim 128");
     constexpr int NW = ATT_THREADS / 64, BQ = ATT_BQ, PPW = AttnDmaGeom<D>::PPW;
     typedef AttnDmaGeom<D> G;
     constexpr int NKS = G::NKS, NDB = G::NDB;
@@ -351,12 +364,13 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p
     const int shift = len_k - len_q;
     int kv_end = len_k;
     if (CAUSAL) kv_end = imin(len_k, q0 + bq + shift);
-    const int n_tiles = (kv_end + ATT_BKV - 1) / ATT_BKV;
+    const int pt = PREFIX ? (p.prefix_len + ATT_BKV - 1) / ATT_BKV : 0;   // prefix tiles: all of them visible to every row
+    const int n_tiles = pt + (kv_end + ATT_BKV - 1) / ATT_BKV;
     const int wave_q_lo = pack ? q0 : q0 + wave * 32, wave_q_hi = wave_q_lo + 31;
     // tiles this wave computes: the later ones are fully masked for its 32 rows (it still issues its DMA pieces and
     // joins the barriers for the other waves in the drain loop below)
     int my_tiles = n_tiles;
-    if (CAUSAL) my_tiles = imax(0, imin(n_tiles, (wave_q_hi + shift) / ATT_BKV + 1));
+    if (CAUSAL) my_tiles = imax(0, imin(n_tiles, pt + (wave_q_hi + shift) / ATT_BKV + 1));
     // split-KV: this workgroup only walks tiles [t_begin, t_end)
     const int t_begin = p.n_splits > 1 ? imin(n_tiles, split * p.split_tiles) : 0;
     const int t_end = p.n_splits > 1 ? imin(n_tiles, t_begin + p.split_tiles) : n_tiles;
@@ -396,11 +410,32 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p
         const int cv = G::VPERM ? att_vchunk72(r & 3, c) : (G::SWZ ? (c ^ ((r & 3) << 2)) : c);
         p_vo[i] = (unsigned)(r * p.ldv + (cv << 3)) * 2u;
     }
+    // the prefix range: its own resources (bound = P rows) and, since its row strides differ from the packed buffer's, its own lane offsets
+    const BufRsrc kp_buf = make_buf(PREFIX ? (const T*)p.k_prefix + kvh * D : k_base, PREFIX ? (unsigned)(((long)(p.prefix_len - 1) * p.ldkp + D) * 2) : 0u);
+    const BufRsrc vp_buf = make_buf(PREFIX ? (const T*)p.v_prefix + kvh * D : v_base, PREFIX ? (unsigned)(((long)(p.prefix_len - 1) * p.ldvp + D) * 2) : 0u);
+    unsigned p_kpo[PREFIX ? PPW : 1], p_vpo[PREFIX ? PPW : 1];
+    if (PREFIX) {
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) {
+            const int ci = (wave + NW * i) * 64 + lane;
+            const int r = ci / G::CH, c = ci - r * G::CH;
+            p_kpo[i] = (unsigned)(r * p.ldkp + ((c ^ (r & 15)) << 3)) * 2u;
+            p_vpo[i] = (unsigned)(r * p.ldvp + ((c ^ ((r & 3) << 2)) << 3)) * 2u;
+        }
+    }
     // piece j of this wave for tile t: j < PPW are its K pieces, the rest its V pieces
     auto issue_piece = [&](int j, int t, int slot) {
         const int i = j < PPW ? j : j - PPW;
         if ((G::PIECES % NW) != 0 && wave + NW * i >= G::PIECES) return;      // wave-uniform; only ragged piece counts (d = 72) branch
         char* dst = smem + slot * 2 * G::TILE_BYTES + (j < PPW ? 0 : G::TILE_BYTES) + (wave + NW * i) * 1024;
+        if (PREFIX) {
+            if (t < pt) {                                          // workgroup-uniform: a prefix tile
+                if (j < PPW) glds16_buf<0>(kp_buf, p_kpo[PREFIX ? i : 0], (unsigned)t * (unsigned)(ATT_BKV * 2) * (unsigned)p.ldkp, dst);
+                else glds16_buf<0>(vp_buf, p_vpo[PREFIX ? i : 0], (unsigned)t * (unsigned)(ATT_BKV * 2) * (unsigned)p.ldvp, dst);
+                return;
+            }
+            t -= pt;                                               // own range: restarts at own row 0
+        }
         if (j < PPW) glds16_buf<STREAM ? 2 : 0>(k_buf, p_ko[i], (unsigned)t * (unsigned)(ATT_BKV * 2) * (unsigned)p.ldk, dst);
         else glds16_buf<STREAM ? 2 : 0>(v_buf, p_vo[i], (unsigned)t * (unsigned)(ATT_BKV * 2) * (unsigned)p.ldv, dst);
     };
@@ -447,7 +482,8 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p
         wait_vmcnt_barrier<0>();                                   // tile t landed; slot of tile t-1 is free
         LMI_PROF_MARK(1);
         LMI_PROF_MARK(2);
-        const int kv0 = t * ATT_BKV;
+        const bool pre_tile = PREFIX && t < pt;
+        const int kv0 = (t - pt) * ATT_BKV;                        // first key of the tile in the sequence's own range (< 0: a prefix tile)
         const char* k_lds = smem + ((t - t_begin) & 1) * 2 * G::TILE_BYTES;
         const char* v_lds = k_lds + G::TILE_BYTES;
 
@@ -491,7 +527,19 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p
         LMI_PROF_MARK(3);
         const bool need_mask = (kv0 + ATT_BKV > len_k) || (CAUSAL && (kv0 + ATT_BKV - 1 > wave_q_lo + shift)) ||
                                (CAUSAL && p.window > 0 && kv0 <= wave_q_hi + shift - p.window);
-        if (need_mask) {
+        if (pre_tile) {
+            // every prefix key is visible to every row; only the last prefix tile has columns past P (zero rows: masked here, in mid-stream)
+            const int plim = p.prefix_len - 1 - t * ATT_BKV;          // last real column of this tile
+            if (plim < ATT_BKV - 1) {
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int col = b * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                        if (col > plim) s[b][r] = -INFINITY;
+                    }
+            }
+        } else if (need_mask) {
             const int lim = CAUSAL ? imin(len_k - 1, my_q + shift) : len_k - 1;   // last visible key
             const int lo = (CAUSAL && p.window > 0) ? my_q + shift - p.window + 1 : 0;   // first visible key
 #pragma unroll

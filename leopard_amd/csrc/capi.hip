@@ -331,6 +331,19 @@ int launch_attn_dma(const AttnArgs& a, int n_seq, int max_q, void* stream) {
     return check_launch("lmi_attn_varlen_fwd");
 }
 
+// Two-range keys (AttnArgs::k_prefix): always the LDS-DMA kernel, its PREFIX instantiation — no other attention kernel knows the prefix range.
+template <typename T>
+int launch_attn_prefix(const AttnArgs& a, int n_seq, int max_q, void* stream) {
+    const int qblocks = (max_q + ATT_BQ - 1) / ATT_BQ;
+    static std::atomic<uint64_t> attr_done{0};
+    allow_big_lds(attn_fwd_dma_kernel<T, 128, true, false, true>, 160 * 1024, attr_done);
+    AttnArgs b = a;
+    b.n_qblocks = qblocks;
+    LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true, false, true>), dim3(qblocks * a.n_heads * n_seq), dim3(ATT_THREADS),
+               AttnDmaGeom<128>::SMEM + g_attn_lds_pad, stream, b);
+    return check_launch("lmi_attn_prefix_fwd");
+}
+
 // Software-pipelined attention (attention64.h): long self-attention prefills at head_dim 128 writing the plain 16-bit output.  OPT-IN
 // (attn.rows64; 0 = attention.h's kernel, the default): measured on the Llama shape (S = 7187, f16; profiles/r04_attention64_study.txt)
 // 1 = two 32-row blocks per wave, one wave per SIMD: 0.572 ms; 2 = one block per wave, two waves per SIMD: 0.505 ms; attention.h 0.442 ms
@@ -352,7 +365,7 @@ int launch_attn_r64(const AttnArgs& a, int n_seq, int max_q, void* stream) {
 template <typename T, int D>
 bool attn_r64_applies(const AttnArgs& a, int max_q, int use_tr) {
     if (D != 128 || !use_tr || !g_attn_dma.load() || !g_attn_rows64.load() || max_q < g_attn_rows64_min.load()) return false;
-    if (!a.out || a.out_fp8 || a.out_f32 || a.out4 || a.n_splits > 1 || a.k_len || a.gqa_pack || a.check_k_extent) return false;   // self-attention, 16-bit output only
+    if (!a.out || a.out_fp8 || a.out_f32 || a.out4 || a.n_splits > 1 || a.k_len || a.gqa_pack || a.check_k_extent || a.k_prefix) return false;   // self-attention, 16-bit output only
     // the ring requests tiles up to two past the end (range-checked to zeros): their 32-bit offsets must not wrap
     return ((long)(max_q + 4 * ATT_BKV) * a.ldk + D) * 2 < (1L << 32) && ((long)(max_q + 4 * ATT_BKV) * a.ldv + D) * 2 < (1L << 32);
 }
@@ -1126,6 +1139,7 @@ static int attn_varlen_entry(const char* who, const void* q, const void* k, cons
     a.out4 = (uint8_t*)out4; a.out4_scale = (uint8_t*)out4_scale; a.ld_out4 = ld_out4; a.ld_out4s = ld_out4s; a.row_sel = row_sel;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale; a.window = window; a.n_qblocks = 0;
     a.n_splits = 1; a.split_tiles = 0; a.part_rows = 0; a.part_o = nullptr; a.part_ml = nullptr; a.gqa_pack = 0;
+    a.k_prefix = nullptr; a.v_prefix = nullptr; a.ldkp = a.ldvp = 0; a.prefix_len = 0;
     a.check_k_extent = 1;
     if (cu_seqlens_k == cu_seqlens_q) {                              // self-attention: the longest key sequence is max_seqlen_q
         if (((long)max_seqlen_q * ldk + head_dim) * 2 >= (1L << 32) || ((long)max_seqlen_q * ldv + head_dim) * 2 >= (1L << 32))
@@ -1217,6 +1231,56 @@ int lmi_attn_varlen_fwd_lo4_rows(const void* q, const void* k, const void* v, vo
     return attn_varlen_entry("lmi_attn_varlen_fwd_lo4", q, k, v, out, nullptr, 0, nullptr, 0, 0.f, cu_seqlens_q, cu_seqlens_k, n_seq, max_seqlen_q, n_heads,
                              n_kv_heads, head_dim, ldq, ldk, ldv, ldo, scale, causal, window, 1, dtype, stream, out4, out4_scale, ld_out4, ld_out4s,
                              (const uint8_t*)row_sel);
+}
+
+// ---- attention over [one shared cached prefix ; the sequence's own new rows] (attention.h PREFIX) --------------------------------
+static int attn_prefix_entry(const char* who, const void* q, const void* k, const void* v, const void* k_prefix, const void* v_prefix, int prefix_len,
+                             void* out, void* out4, void* out4_scale, int ld_out4, int ld_out4s, const uint8_t* row_sel, const int* cu_seqlens, int n_seq,
+                             int max_seqlen_q, int n_heads, int n_kv_heads, int head_dim, int ldq, int ldk, int ldv, int ldkp, int ldvp, int ldo, float scale,
+                             int dtype, void* stream) {
+    if (!q || !k || !v || !k_prefix || !v_prefix || !out || !cu_seqlens) return fail(LMI_EINVAL, "%s: null pointer", who);
+    if (head_dim != 128) return fail(LMI_EINVAL, "%s: head_dim %d (only 128)", who, head_dim);
+    if (prefix_len < 1) return fail(LMI_EINVAL, "%s: prefix_len %d (need >= 1)", who, prefix_len);
+    if (n_seq < 0 || max_seqlen_q < 0 || n_heads <= 0 || n_kv_heads <= 0 || (n_heads % n_kv_heads))
+        return fail(LMI_EINVAL, "%s: bad head counts (%d, %d)", who, n_heads, n_kv_heads);
+    if (!g_attn_dma.load()) return fail(LMI_EINVAL, "%s: needs the LDS-DMA kernel (attn.dma = 1)", who);
+    if (out4 && (!out4_scale || ((uintptr_t)out4 & 7) || (ld_out4 & 7) || ld_out4 < n_heads * 4 * 16 || ld_out4s < n_heads * 4))
+        return fail(LMI_EINVAL, "%s: the residual image needs an 8-byte aligned image with ld_out4 %% 8 == 0 and >= n_heads * 64 bytes, ld_out4s >= n_heads * 4", who);
+    if ((ldq & 7) || (ldk & 7) || (ldv & 7) || (ldkp & 7) || (ldvp & 7) || (ldo & 7) || ldq < n_heads * 128 || ldo < n_heads * 128 || ldk < n_kv_heads * 128 ||
+        ldv < n_kv_heads * 128 || ldkp < n_kv_heads * 128 || ldvp < n_kv_heads * 128 || !aligned16(q) || !aligned16(k) || !aligned16(v) ||
+        !aligned16(k_prefix) || !aligned16(v_prefix) || !aligned16(out))
+        return fail(LMI_EINVAL, "%s: alignment / row strides", who);
+    // 32-bit buffer offsets: the prefix rows, and the longest own range, each span < 4 GiB — and so does their sum, the rule a contiguous
+    // [prefix ; own] launch of the same keys would be held to
+    const long own = (long)max_seqlen_q * (ldk > ldv ? ldk : ldv), pre = (long)prefix_len * (ldkp > ldvp ? ldkp : ldvp);
+    if ((own + pre + head_dim) * 2 >= (1L << 32))
+        return fail(LMI_EINVAL, "%s: prefix + own K / V rows span >= 4 GiB (prefix_len %d, max_seqlen %d)", who, prefix_len, max_seqlen_q);
+    if (n_seq == 0 || max_seqlen_q == 0) return LMI_OK;
+    AttnArgs a;
+    a.q = q; a.k = k; a.v = v; a.out = out; a.cu_q = cu_seqlens; a.cu_k = cu_seqlens; a.k_len = nullptr;
+    a.out_fp8 = nullptr; a.ldo8 = 0; a.out_fp8_scale = 0.f; a.out_f32 = nullptr; a.ldo32 = 0;
+    a.out4 = (uint8_t*)out4; a.out4_scale = (uint8_t*)out4_scale; a.ld_out4 = ld_out4; a.ld_out4s = ld_out4s; a.row_sel = row_sel;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale; a.window = 0; a.n_qblocks = 0;
+    a.n_splits = 1; a.split_tiles = 0; a.part_rows = 0; a.part_o = nullptr; a.part_ml = nullptr; a.gqa_pack = 0; a.check_k_extent = 0;
+    a.k_prefix = k_prefix; a.v_prefix = v_prefix; a.ldkp = ldkp; a.ldvp = ldvp; a.prefix_len = prefix_len;
+    LMI_DISPATCH_T(dtype, (launch_attn_prefix<f16_t>(a, n_seq, max_seqlen_q, stream)), (launch_attn_prefix<bf16_t>(a, n_seq, max_seqlen_q, stream)));
+}
+
+int lmi_attn_prefix_fwd(const void* q, const void* k, const void* v, const void* k_prefix, const void* v_prefix, int prefix_len, void* out,
+                        const int* cu_seqlens, int n_seq, int max_seqlen_q, int n_heads, int n_kv_heads, int head_dim, int ldq, int ldk, int ldv,
+                        int ldkp, int ldvp, int ldo, float scale, int dtype, void* stream) {
+    return attn_prefix_entry("lmi_attn_prefix_fwd", q, k, v, k_prefix, v_prefix, prefix_len, out, nullptr, nullptr, 0, 0, nullptr, cu_seqlens, n_seq, max_seqlen_q,
+                             n_heads, n_kv_heads, head_dim, ldq, ldk, ldv, ldkp, ldvp, ldo, scale, dtype, stream);
+}
+
+int lmi_attn_prefix_fwd_lo4_rows(const void* q, const void* k, const void* v, const void* k_prefix, const void* v_prefix, int prefix_len, void* out,
+                                 void* out4, void* out4_scale, int ld_out4, int ld_out4s, const int* cu_seqlens, int n_seq, int max_seqlen_q, int n_heads,
+                                 int n_kv_heads, int head_dim, int ldq, int ldk, int ldv, int ldkp, int ldvp, int ldo, float scale, const void* row_sel,
+                                 int dtype, void* stream) {
+    if (!out4 || !out4_scale) return fail(LMI_EINVAL, "lmi_attn_prefix_fwd_lo4_rows: null pointer");
+    return attn_prefix_entry("lmi_attn_prefix_fwd_lo4_rows", q, k, v, k_prefix, v_prefix, prefix_len, out, out4, out4_scale, ld_out4, ld_out4s,
+                             (const uint8_t*)row_sel, cu_seqlens, n_seq, max_seqlen_q, n_heads, n_kv_heads, head_dim, ldq, ldk, ldv, ldkp, ldvp, ldo, scale,
+                             dtype, stream);
 }
 
 int lmi_attn_varlen_fwd_lo4(const void* q, const void* k, const void* v, void* out, void* out4, void* out4_scale, int ld_out4, int ld_out4s,
@@ -1314,6 +1378,7 @@ static int attn_decode_entry(const char* who, const void* q, const void* k, cons
     a.out_fp8 = nullptr; a.ldo8 = 0; a.out_fp8_scale = 0.f; a.out_f32 = nullptr; a.ldo32 = 0;
     a.out4 = nullptr; a.out4_scale = nullptr; a.ld_out4 = a.ld_out4s = 0; a.row_sel = nullptr;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale; a.window = window;
+    a.k_prefix = nullptr; a.v_prefix = nullptr; a.ldkp = a.ldvp = 0; a.prefix_len = 0;
     if (((long)max_seqlen_k * ldk + head_dim) * 2 >= (1L << 32) || ((long)max_seqlen_k * ldv + head_dim) * 2 >= (1L << 32))
         return fail(LMI_EINVAL, "%s: one sequence's K / V rows span >= 4 GiB (max_seqlen_k %d, ldk %d, ldv %d)", who, max_seqlen_k, ldk, ldv);
     a.check_k_extent = 0;

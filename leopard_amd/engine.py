@@ -95,6 +95,15 @@ class ScoreResult:
     seq_len: int
 
 
+@dataclass
+class ExtendResult:
+    """LeopardEngine.extend: N text suffixes continued from one cached prefix."""
+    logits: torch.Tensor                         # fp32 [N, vocab]: the last row of every suffix
+    seq_lens: List[int]                          # the suffix lengths s_j (rows; suffixes are text only)
+    prefix_len: int                              # P: suffix j's rows sit at positions P .. P + s_j - 1
+    kv_out: Optional["KVCache"] = None           # the suffixes' K / V at packed row offsets (sum of the earlier s_j), when asked for
+
+
 class KVCache:
     def __init__(self, cfg: LeopardConfig, capacity: int, dtype, device, tp_size: int = 1):
         tc = cfg.text_config
@@ -796,7 +805,8 @@ class LeopardEngine:
             if self.trace:
                 self.trace(f"vit.{li}", x)
 
-    def _llm_layers_lo4(self, x, cache, cu, cos, sin, max_len, seq_lens=None, all_rows=False, extra_rows=None):
+    def _llm_layers_lo4(self, x, cache, cu, cos, sin, max_len, seq_lens=None, all_rows=False, extra_rows=None, prefix=None, cache_pos0=0,
+                        cu_k=None):
         """The Llama / Mistral layers with the low-bit correction phase, on the FUSED schedule of the fast path: the RMSNorms ride in the GEMM
         epilogues (the producers o_proj / down_proj also write the fp4 image of the residual of T(x gamma)), q|k|v + RoPE + KV append is one
         launch, gate/up's SwiGLU epilogue writes down_proj's operand pair, the attention kernel o_proj's: no launch is added to the fast schedule."""
@@ -822,9 +832,8 @@ class LeopardEngine:
             if i == 0:
                 ops.norm_lo4(x, L.in_norm, None, h, tc.rms_norm_eps)
             ops.rmsnorm_rope_lo4(h, L.qkv_w_rope, qkv4, qkv, None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin,
-                                 cache.k[i] if cache else None, cache.v[i] if cache else None, 0, H, KV, hd)
-            ops.attention_lo4(qkv[:, :qw], qkv[:, qw:qw + kw], qkv[:, qw + kw:], att, cu, cu, max_len, H, KV, hd, scale, True,
-                              window=tc.sliding_window or 0)
+                                 cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0, H, KV, hd)
+            self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)
             ops.gemm_lo4(att, L.o_w, o4, x, epilogue=_lib.EPI_RESIDUAL, norm_out=h.hi, norm_gamma=L.post_norm, rowsq_out=sq_a, out4=h)
             ops.gemm_lo4(h, L.gu_w, gu4, gu.hi, epilogue=_lib.EPI_SWIGLU, rowsq_in=sq_a, norm_dim=D, norm_eps=tc.rms_norm_eps, out4=gu)
             if i + 1 < n_layers:
@@ -967,9 +976,35 @@ class LeopardEngine:
             cache.length = S
         return (None, None) if score_rows is not None else self._lm_head(x, last_rows, all_logits)
 
-    def _llm_layers_fast(self, x, cache, cu, cos, sin, max_len):
+    def _attend(self, i, qkv, att, cu, max_len, cache, prefix, cu_k):
+        """The attention launch of layer i over the packed q|k|v rows.  ``att``: the 16-bit output rows, or the Lo4Act of the lo4 schedule.
+        Default: causal self-attention of the packed sequences.  ``prefix`` (extend): every sequence's keys are [the P cached rows of
+        ``prefix`` ; its own rows] — the two-range launch, the prefix read in place.  ``cu_k`` (append): the keys are the rows of ``cache``
+        itself, which the q|k|v epilogue has just extended."""
+        ops, tc = self.ops, self.cfg.text_config
+        (H, KV), hd = self._llm_heads(), tc.head_dim
+        qw, kw = H * hd, KV * hd
+        q, k, v = qkv[:, :qw], qkv[:, qw:qw + kw], qkv[:, qw + kw:]
+        lo4 = not isinstance(att, torch.Tensor)
+        if prefix is not None:
+            P = prefix.length
+            if lo4:
+                ops.attention_prefix_lo4(q, k, v, prefix.k[i][:P], prefix.v[i][:P], P, att, cu, max_len, H, KV, hd, hd ** -0.5)
+            else:
+                ops.attention_prefix(q, k, v, prefix.k[i][:P], prefix.v[i][:P], P, att, cu, max_len, H, KV, hd, hd ** -0.5)
+            return
+        if cu_k is not None:
+            k, v = cache.k[i], cache.v[i]
+        if lo4:
+            ops.attention_lo4(q, k, v, att, cu, cu if cu_k is None else cu_k, max_len, H, KV, hd, hd ** -0.5, True, window=tc.sliding_window or 0)
+        else:
+            ops.attention(q, k, v, att, cu, cu if cu_k is None else cu_k, max_len, H, KV, hd, hd ** -0.5, True, self.use_tr,
+                          window=tc.sliding_window or 0)
+
+    def _llm_layers_fast(self, x, cache, cu, cos, sin, max_len, prefix=None, cache_pos0=0, cu_k=None):
         """The Llama / Mistral layers of the fast schedule, on the caller-owned workspace: fused (the norms and the RoPE ride in the GEMM
-        epilogues) where the shapes allow it, launch by launch otherwise (also the tensor-parallel packed prefill and the calibration pass)."""
+        epilogues) where the shapes allow it, launch by launch otherwise (also the tensor-parallel packed prefill and the calibration pass).
+        ``prefix`` / ``cache_pos0`` / ``cu_k``: continuing from cached rows (extend / append; _attend)."""
         ops, W, tc = self.ops, self.W, self.cfg.text_config
         S, D = x.shape
         (H, KV), hd = self._llm_heads(), tc.head_dim
@@ -993,9 +1028,8 @@ class LeopardEngine:
                 if i == 0:
                     ops.rmsnorm(x, L.in_norm, h, tc.rms_norm_eps)
                 ops.rmsnorm_rope(h, L.qkv_w_rope, qkv, None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin,
-                                 cache.k[i] if cache else None, cache.v[i] if cache else None, 0, H, KV, hd)
-                ops.attention(qkv[:, :qw], qkv[:, qw:qw + kw], qkv[:, qw + kw:], att, cu, cu, max_len, H, KV, hd, scale,
-                              True, self.use_tr, window=tc.sliding_window or 0)
+                                 cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0, H, KV, hd)
+                self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)
                 ops.gemm_ex(att, L.o_w, x, epilogue=_lib.EPI_RESIDUAL, norm_out=h, norm_gamma=L.post_norm, rowsq_out=sq_a)
                 ops.gemm_ex(h, L.gu_w, gu, epilogue=_lib.EPI_SWIGLU, rowsq_in=sq_a, norm_dim=D, norm_eps=tc.rms_norm_eps)
                 if i + 1 < n_layers:
@@ -1011,14 +1045,13 @@ class LeopardEngine:
                 rec and rec(("llm", i, "h1"), h)
                 if L.qkv_w is not None:
                     ops.gemm(h, L.qkv_w, qkv)
-                    ops.rope_qk(qkv, H, KV, hd, cos, sin, cache.k[i] if cache else None, cache.v[i] if cache else None, 0)
+                    ops.rope_qk(qkv, H, KV, hd, cos, sin, cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0)
                 else:                                    # packed weights keep the rope-ordered rows only: projection + RoPE + KV append on the normalised rows
                     ops.rmsnorm_rope(h, L.qkv_w_rope, qkv, None, tc.rms_norm_eps, cos, sin, cache.k[i] if cache else None,
-                                     cache.v[i] if cache else None, 0, H, KV, hd)
+                                     cache.v[i] if cache else None, cache_pos0, H, KV, hd)
                 if rec:                                  # operands of the fp8 attention arithmetic (rotated q / k, v)
                     rec(("llm", i, "q"), qkv[:, :qw]); rec(("llm", i, "k"), qkv[:, qw:qw + kw]); rec(("llm", i, "v"), qkv[:, qw + kw:])
-                ops.attention(qkv[:, :qw], qkv[:, qw:qw + kw], qkv[:, qw + kw:], att, cu, cu, max_len, H, KV, hd, scale,
-                              True, self.use_tr, window=tc.sliding_window or 0)
+                self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)
                 rec and rec(("llm", i, "att"), att)
                 self._row_parallel(att, L.o_w, x, tmp)
                 ops.rmsnorm(x, L.post_norm, h, tc.rms_norm_eps)
@@ -2052,3 +2085,177 @@ class LeopardEngine:
         outs = self._greedy_loop_batch(st, prompts, first, seq_lens, max_new_tokens, eos,
                                        None if sampling is None else [req(j) for j in range(len(samples))])
         return [torch.tensor([o], dtype=torch.long, device=ids.device) for o, (ids, _) in zip(outs, samples)]
+
+
+    # ------------------------------------------------------------------------------------------------
+    # Continuing from a cached prefix: N new row ranges against rows that are already in a KV cache.  ``extend`` fans one read-only prefix
+    # out to N packed text suffixes (the two-range attention launch, csrc/attention.h PREFIX: the prefix K / V are read in place, never
+    # copied per suffix); ``append`` grows one cache in place by n rows (multi-turn); ``generate_shared`` = one prefill of the shared
+    # prompt head (the vision tower runs once) + extend + the unchanged batched decode.
+    # ------------------------------------------------------------------------------------------------
+    def _continuation_guard(self, what: str) -> None:
+        tc = self.cfg.text_config
+        if self.tp_size > 1:
+            raise NotImplementedError(f"{what}: tensor-parallel engines are not supported (the two-range attention launch runs on one rank)")
+        if self.fp8 is not None:
+            raise NotImplementedError(f"{what}: the fp8 schedule is not supported (its attention operands have no prefix form); use 'fast' or 'lo4'")
+        if self.split_operands:
+            raise NotImplementedError(f"{what}: precision 'split' is not supported (its attention hands over fp32 rows); use 'fast' or 'lo4'")
+        if (tc.sliding_window or 0) > 0:
+            raise NotImplementedError(f"{what}: sliding_window = {tc.sliding_window} is not supported (the prefix range has no window)")
+
+    def _text_suffixes(self, what: str, suffixes) -> List[torch.Tensor]:
+        out = []
+        for j, ids in enumerate(suffixes):
+            ids = ids.reshape(1, -1)
+            if ids.numel() == 0:
+                raise ValueError(f"{what}: suffix {j} is empty")
+            if bool((ids == self.cfg.image_token_index).any()):
+                raise ValueError(f"{what}: suffix {j} holds an image token (images belong to the prefix)")
+            out.append(ids)
+        if not out:
+            raise ValueError(f"{what}: no suffix")
+        return out
+
+    def _continuation_geometry(self, P: int, lens: Sequence[int]):
+        """sequence_geometry for rows that start at position P of their sequence: cu_seqlens, RoPE tables of positions P .. P + l - 1, last rows."""
+        key = ("ext", int(P), tuple(int(l) for l in lens))
+        hit = self._geom_cache.get(key)
+        if hit is None:
+            cu_list = [0] + [int(c) for c in np.cumsum(key[2])]
+            cu = torch.tensor(cu_list, dtype=torch.int32, device=self.device)
+            cos, sin = self.rope_tables(torch.cat([torch.arange(P, P + l) for l in key[2]]))
+            last_rows = torch.tensor([c - 1 for c in cu_list[1:]], device=self.device)
+            if len(self._geom_cache) > 64:
+                self._geom_cache.clear()
+            hit = self._geom_cache[key] = (cu, cos, sin, last_rows, cu_list)
+        return hit
+
+    @torch.no_grad()
+    def extend(self, prefix: KVCache, suffixes: Sequence[torch.Tensor], kv_out: Optional[KVCache] = None) -> ExtendResult:
+        """Run N text-only suffixes ([1, s_j] ids, s_j >= 1) against ONE cached prefix: ``prefix`` is any cache a ``prefill(ids, tiles,
+        cache=...)`` filled (P = prefix.length rows).  The suffix rows are embedded, packed, rotated at positions P .. P + s_j - 1 and run
+        through the layers of the current precision ("fast" or "lo4"); their attention sees [the P prefix rows ; their own rows] through the
+        two-range launch, so the prefix K / V are read in place once per layer whatever N is.  ``kv_out`` receives the suffixes' K / V at
+        packed row offsets (kv_out.length = sum s_j).  ``prefix`` is never written: it can be extended any number of times.  Under lo4 the
+        row selection applies to the suffix lengths (a suffix of <= LO4_FULL_BELOW rows is corrected whole); the prefix rows keep the
+        schedule of their own prefill.  Not bit-identical to a from-scratch prefill of [prefix ; suffix] (another key-tile partition unless
+        P % 64 == 0, and another row selection); held to the same tolerances against the fp32 oracle."""
+        self._continuation_guard("extend")
+        P = int(prefix.length)
+        if P < 1:
+            raise ValueError("extend: the prefix cache is empty (prefill it first)")
+        sfx = self._text_suffixes("extend", suffixes)
+        lens = [int(t.numel()) for t in sfx]
+        S = sum(lens)
+        if kv_out is not None:
+            if kv_out is prefix:
+                raise ValueError("extend: kv_out must not be the prefix cache (extend never writes into the prefix; see append)")
+            if kv_out.capacity < S:
+                raise ValueError(f"extend: kv_out holds {kv_out.capacity} rows, the suffixes have {S}")
+        if self.cfg.text_config.head_dim != 128:
+            raise NotImplementedError("extend: the two-range attention launch needs head_dim 128")
+        xs = [self.embed_merge(t, None) for t in sfx]
+        x = torch.cat(xs, dim=0) if len(xs) > 1 else xs[0]
+        cu, cos, sin, last_rows, _ = self._continuation_geometry(P, lens)
+        self.llm_packed
+        self.last_lo4_ranges = None
+        if self.lo4:
+            self._llm_layers_lo4(x, kv_out, cu, cos, sin, max(lens), lens, prefix=prefix)
+        else:
+            self._llm_layers_fast(x, kv_out, cu, cos, sin, max(lens), prefix=prefix)
+        if kv_out is not None:
+            kv_out.length = S
+        last, _ = self._lm_head(x, last_rows, False)
+        return ExtendResult(logits=last, seq_lens=lens, prefix_len=P, kv_out=kv_out)
+
+    @torch.no_grad()
+    def append(self, cache: KVCache, ids: torch.Tensor) -> torch.Tensor:
+        """Multi-turn: n more text ids onto ``cache`` IN PLACE.  Their K / V go to rows P .. P + n - 1 (P = cache.length), their attention is the
+        existing varlen kernel over the cache rows (cu_q = [0, n], cu_k = [0, P + n], bottom-right causal), cache.length advances by n and
+        the logits of the n new rows come back, fp32 [n, vocab].  The batch-1 decode state of the cache reads its position and key count
+        from cache.length at every step, so it stays valid."""
+        self._continuation_guard("append")
+        P = int(cache.length)
+        if P < 1:
+            raise ValueError("append: the cache is empty (prefill it first)")
+        ids = self._text_suffixes("append", [ids])[0]
+        n = int(ids.numel())
+        if P + n > cache.capacity:
+            raise ValueError(f"append: {P} + {n} rows exceed the cache capacity {cache.capacity}")
+        x = self.embed_merge(ids, None)
+        cu, cos, sin, last_rows, _ = self._continuation_geometry(P, [n])
+        ck = ("ext_k", P, n)
+        cu_k = self._geom_cache.get(ck)
+        if cu_k is None:
+            cu_k = self._geom_cache[ck] = torch.tensor([0, P + n], dtype=torch.int32, device=self.device)
+        self.llm_packed
+        self.last_lo4_ranges = None
+        if self.lo4:
+            self._llm_layers_lo4(x, cache, cu, cos, sin, n, [n], all_rows=True, cache_pos0=P, cu_k=cu_k)
+        else:
+            self._llm_layers_fast(x, cache, cu, cos, sin, n, cache_pos0=P, cu_k=cu_k)
+        cache.length = P + n
+        _, logits = self._lm_head(x, last_rows, True)
+        return logits
+
+    @torch.no_grad()
+    def generate_shared(self, prefix_ids: torch.Tensor, tiles: Optional[torch.Tensor], suffixes: Sequence[torch.Tensor],
+                        max_new_tokens: int = 128, eos_token_id: Sequence[int] = (128001, 128009),
+                        sampling: Optional[SamplingParams] = None, prefix: Optional[KVCache] = None) -> List[torch.Tensor]:
+        """N prompts that share their head — ``prefix_ids`` with all the images (``tiles``) — and differ in a text suffix (the question):
+        ONE prefill of the prefix (the vision tower runs once) into a cache of exactly P rows, ONE ``extend`` of the N suffixes, then request
+        j's rows — the P prefix rows and its own s_j — are copied into decode slot j and the batch continues through the unchanged batched
+        decode (N = 1 and shapes without batched-decode support: the batch-1 cache).  More than MAX_DECODE_BATCH suffixes run in chunks that
+        share the one prefix prefill.  Request i samples with ``sampling.for_request(i)``.  Each output is [1, len(prefix_ids) + len(suffix_j)
+        + T]: what ``generate`` returns for the concatenated prompt (same rule; tokens can differ on a near tie of the top two logits).
+        The decode slots do NOT share the prefix: each holds its own copy, so the decode pool is B x (P + s + T) rows per layer (a
+        shared-prefix decode attention is the follow-up); what is saved is the prefill — tower and LLM rows fall from N x (P + s) to P + N x s.
+        ``prefix``: a cache that a ``prefill(prefix_ids, tiles, cache=prefix)`` has already filled — the prefill is skipped (``tiles`` is not
+        read) and, as with ``extend``, the cache is left untouched."""
+        self._continuation_guard("generate_shared")
+        sfx = self._text_suffixes("generate_shared", suffixes)
+        pids = prefix_ids.reshape(1, -1)
+        if pids.numel() == 0:
+            raise ValueError("generate_shared: the prefix is empty")
+        P = self.merged_len(pids)
+        if prefix is None:
+            prefix = KVCache(self.cfg, P, self.dtype, self.device)
+            self.prefill(pids, tiles, cache=prefix)
+        elif prefix.length != P:
+            raise ValueError(f"generate_shared: the prefix cache holds {prefix.length} rows, prefix_ids merge to {P}")
+        eos = set(int(e) for e in eos_token_id)
+        head = [int(t) for t in pids.reshape(-1).tolist()]
+        outs: List[torch.Tensor] = []
+        for c0 in range(0, len(sfx), self.MAX_DECODE_BATCH):
+            chunk = sfx[c0:c0 + self.MAX_DECODE_BATCH]
+            req = [None if sampling is None else sampling.for_request(c0 + j) for j in range(len(chunk))]
+            lens = [int(t.numel()) for t in chunk]
+            decode = max_new_tokens > 1
+            kv = KVCache(self.cfg, sum(lens), self.dtype, self.device) if decode else None
+            res = self.extend(prefix, chunk, kv_out=kv)
+            if sampling is None:
+                first = [self.first_token(res.logits[j]) for j in range(len(chunk))]
+            else:
+                first = self.sample_first(res.logits, req)
+            prompts = [head + [int(t) for t in ids.reshape(-1).tolist()] for ids in chunk]
+            offs = [0] + [int(c) for c in np.cumsum(lens)]
+            if not decode:
+                toks = [p + [f] for p, f in zip(prompts, first)] if max_new_tokens == 1 else prompts
+            elif len(chunk) == 1 or not self._batch_decode_supported():
+                toks = []
+                for j, s in enumerate(lens):
+                    cache = self._generation_cache(P + s + max_new_tokens)
+                    self._move_kv(prefix, 0, P, cache.k, cache.v, 0)
+                    self._move_kv(kv, offs[j], s, cache.k, cache.v, P)
+                    cache.length = P + s
+                    toks.append(self._greedy_loop(prompts[j], first[j], cache, max_new_tokens, eos, req[j]))
+            else:
+                st = self._batch_state(len(chunk), P + max(lens) + max_new_tokens)
+                for j, s in enumerate(lens):
+                    self._move_kv(prefix, 0, P, st.k, st.v, j * st.capacity)
+                    self._move_kv(kv, offs[j], s, st.k, st.v, j * st.capacity + P)
+                toks = self._greedy_loop_batch(st, prompts, first, [P + s for s in lens], max_new_tokens, eos,
+                                               None if sampling is None else req)
+            outs += [torch.tensor([o], dtype=torch.long, device=ids.device) for o, ids in zip(toks, chunk)]
+        return outs

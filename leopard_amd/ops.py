@@ -214,6 +214,14 @@ class Ops:
                                                  int(window), int(use_tr), _DT[q.dtype], self._stream(out)))
         return out
 
+    def attention_prefix(self, q, k, v, k_prefix, v_prefix, prefix_len, out, cu, max_seqlen_q, n_heads, n_kv_heads, head_dim, scale):
+        """lmi_attn_prefix_fwd: causal self-attention of the packed sequences ``cu`` whose keys are [k_prefix / v_prefix rows 0 .. prefix_len) ;
+        own rows] — the shared prefix (2-D row views, e.g. one layer of a KV cache) is read in place, once per launch, and never written."""
+        self._check(self.lib.lmi_attn_prefix_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(k_prefix), _ptr(v_prefix), int(prefix_len), _ptr(out), _ptr(cu),
+                                                 cu.numel() - 1, int(max_seqlen_q), n_heads, n_kv_heads, head_dim, q.stride(0), k.stride(0), v.stride(0),
+                                                 k_prefix.stride(0), v_prefix.stride(0), out.stride(0), float(scale), _DT[q.dtype], self._stream(out)))
+        return out
+
     def attention_decode(self, q, k, v, out, cu_q, cu_k, max_seqlen_q, max_seqlen_k, n_heads, n_kv_heads, head_dim, scale,
                          workspace: torch.Tensor, window=0, hl=False):
         """Split-KV attention for a few query rows against a long cache (decode).  workspace: fp32, decode_workspace_elems().
@@ -506,6 +514,16 @@ class Ops:
                                                           act.sc.stride(0), _ptr(cu_q), _ptr(cu_k), n_seq, int(max_seqlen_q), n_heads, n_kv_heads, head_dim,
                                                           q.stride(0), k.stride(0), v.stride(0), act.hi.stride(0), float(scale), int(bool(causal)),
                                                           int(window), _ptr(act.row_sel), _DT[q.dtype], self._stream(act.hi)))
+        return act
+
+    def attention_prefix_lo4(self, q, k, v, k_prefix, v_prefix, prefix_len, act: Lo4Act, cu, max_seqlen_q, n_heads, n_kv_heads, head_dim, scale):
+        """lmi_attn_prefix_fwd_lo4_rows: attention_prefix writing act.hi and, for the rows act.row_sel selects, the residual image (attention_lo4)."""
+        assert act.K4 == lo4_head_k4(n_heads, head_dim)
+        self._check(self.lib.lmi_attn_prefix_fwd_lo4_rows(_ptr(q), _ptr(k), _ptr(v), _ptr(k_prefix), _ptr(v_prefix), int(prefix_len), _ptr(act.hi),
+                                                          _ptr(act.img), _ptr(act.sc), act.img.stride(0), act.sc.stride(0), _ptr(cu), cu.numel() - 1,
+                                                          int(max_seqlen_q), n_heads, n_kv_heads, head_dim, q.stride(0), k.stride(0), v.stride(0),
+                                                          k_prefix.stride(0), v_prefix.stride(0), act.hi.stride(0), float(scale), _ptr(act.row_sel),
+                                                          _DT[q.dtype], self._stream(act.hi)))
         return act
 
     def split_lo4(self, x_f32: torch.Tensor, act: Lo4Act) -> Lo4Act:
