@@ -180,7 +180,15 @@ int lmi_gemm_ex(const void* A, const void* W, void* out, const float* bias, int 
  * Wqkv: [(n_q + 2 n_kv) * 128, K]; the 128 rows of every q and k head must be stored in the order
  * d = 0..31, 64..95, 32..63, 96..127 (leopard_amd.weights.rope_permute_rows), so that the 64 output columns a wave owns hold 32
  * first-half elements and their rotate-half partners; the epilogue restores the natural order on store.  cos/sin: fp32
- * [M, 64] per packed row.  k_cache / v_cache (nullable): rotated K and V also go to cache rows cache_pos0 + m.  head_dim = 128. */
+ * [M, 64] per packed row.  k_cache / v_cache (nullable): rotated K and V also go to cache rows cache_pos0 + m.  head_dim = 128.
+ * Head subsets (one of the two counts may be 0; Wqkv / qkv then point at that part's first row / column, N = the part's width):
+ *   n_q_heads == 0:  the k | v columns alone — Wqkv = the 2 n_kv * 128 rows of k then v, qkv[m] = [ RoPE(k), v ], caches appended as above;
+ *   n_kv_heads == 0: the q columns alone — Wqkv = the n_q * 128 rows of q, qkv[m] = [ RoPE(q) ]; k_cache / v_cache must be null.
+ * A row-major Wqkv is sliced by rows, a packed one at any multiple of 16 rows (its 16-row groups are contiguous), the lo4 weight image and
+ * scales by rows.  Every output and cache element is bit for bit the one the full launch over the same rows writes to that column, and a
+ * row's bits do not depend on M or on where the row sits in the launch (the k order of the accumulation is the same in every tile
+ * geometry): a q-only launch over a trailing row window equals those rows of the full launch.  cos / sin, rowsq_in, and under lo4 the
+ * images, row_sel, unit_sel (window start % 64 == 0) and sel_ranges are then the window's own rows. */
 int lmi_rmsnorm_rope(const void* A, const void* Wqkv, void* qkv, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_table,
                      const float* sin_table, void* k_cache, void* v_cache, int ld_cache, int cache_pos0, int M, int n_q_heads, int n_kv_heads,
                      int head_dim, int K, int lda, int ldw, int ldo, int dtype, void* stream);
@@ -282,7 +290,8 @@ typedef struct lmi_lo4 {
     const void* row_sel; const void* unit_sel;
     const int* sel_ranges; int n_sel_ranges;
 } lmi_lo4;
-/* lmi_gemm_ex / lmi_rmsnorm_rope with the correction phase (plain A, row-major or packed W for the 16-bit pass, K >= 128). */
+/* lmi_gemm_ex / lmi_rmsnorm_rope with the correction phase (plain A, row-major or packed W for the 16-bit pass, K >= 128).
+ * lmi_rmsnorm_rope_lo4 takes the head subsets of lmi_rmsnorm_rope (n_q_heads == 0 / n_kv_heads == 0): w4 / w4_scale point at the part's rows. */
 int lmi_gemm_lo4(const void* A, const void* W, void* out, const float* bias, int M, int N, int K, int lda, int ldw, int ldo, int epilogue, int act,
                  const float* rowsq_in, int rowsq_parts, int norm_dim, float norm_eps, void* norm_out, const float* norm_gamma, float* rowsq_out,
                  int ld_norm, const lmi_lo4* lo, int dtype, void* stream);

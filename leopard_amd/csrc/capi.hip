@@ -948,13 +948,22 @@ int lmi_gemm_ex(const void* A, const void* W, void* out, const float* bias, int 
                       stream, x);
 }
 
+// argument checks lmi_rmsnorm_rope and lmi_rmsnorm_rope_lo4 share.  Head subsets: n_q_heads == 0 = the k | v columns alone, n_kv_heads == 0 = the
+// q columns alone (no cache: nothing of it is K or V)
+static int rope_entry_check(const char* who, const float* cos_table, const float* sin_table, const void* k_cache, const void* v_cache, int ld_cache,
+                            int n_q_heads, int n_kv_heads, int head_dim, int ldo) {
+    if (head_dim != 128) return fail(LMI_EINVAL, "%s: head_dim %d (only 128: a wave's 64 columns hold half a head)", who, head_dim);
+    if (!cos_table || !sin_table || n_q_heads < 0 || n_kv_heads < 0 || n_q_heads + n_kv_heads == 0 || ((k_cache != nullptr) != (v_cache != nullptr)) ||
+        (k_cache && (n_kv_heads == 0 || (ld_cache & 7) || !aligned16(k_cache) || !aligned16(v_cache))) || (ldo & 7) || !aligned16(cos_table) ||
+        !aligned16(sin_table))
+        return fail(LMI_EINVAL, "%s: bad argument", who);
+    return LMI_OK;
+}
+
 int lmi_rmsnorm_rope(const void* A, const void* Wqkv, void* qkv, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_table,
                      const float* sin_table, void* k_cache, void* v_cache, int ld_cache, int cache_pos0, int M, int n_q_heads, int n_kv_heads,
                      int head_dim, int K, int lda, int ldw, int ldo, int dtype, void* stream) {
-    if (head_dim != 128) return fail(LMI_EINVAL, "lmi_rmsnorm_rope: head_dim %d (only 128: a wave's 64 columns hold half a head)", head_dim);
-    if (!cos_table || !sin_table || n_q_heads <= 0 || n_kv_heads <= 0 || ((k_cache != nullptr) != (v_cache != nullptr)) ||
-        (k_cache && ((ld_cache & 7) || !aligned16(k_cache) || !aligned16(v_cache))) || (ldo & 7) || !aligned16(cos_table) || !aligned16(sin_table))
-        return fail(LMI_EINVAL, "lmi_rmsnorm_rope: bad argument");
+    if (const int rc = rope_entry_check("lmi_rmsnorm_rope", cos_table, sin_table, k_cache, v_cache, ld_cache, n_q_heads, n_kv_heads, head_dim, ldo)) return rc;
     GemmExtras x;
     x.rowsq_in = rowsq_in; x.rowsq_parts = rowsq_parts; x.norm_dim = K; x.norm_eps = norm_eps;
     x.rope_cos = cos_table; x.rope_sin = sin_table; x.k_cache = k_cache; x.v_cache = v_cache; x.ld_cache = ld_cache; x.cache_pos0 = cache_pos0;
@@ -980,10 +989,7 @@ int lmi_rmsnorm_rope_lo4(const void* A, const void* Wqkv, void* qkv, const float
                          const float* sin_table, void* k_cache, void* v_cache, int ld_cache, int cache_pos0, int M, int n_q_heads, int n_kv_heads,
                          int head_dim, int K, int lda, int ldw, int ldo, const lmi_lo4* lo, int dtype, void* stream) {
     if (!lo) return fail(LMI_EINVAL, "lmi_rmsnorm_rope_lo4: null lo4 descriptor (use lmi_rmsnorm_rope)");
-    if (head_dim != 128) return fail(LMI_EINVAL, "lmi_rmsnorm_rope_lo4: head_dim %d (only 128: a wave's 64 columns hold half a head)", head_dim);
-    if (!cos_table || !sin_table || n_q_heads <= 0 || n_kv_heads <= 0 || ((k_cache != nullptr) != (v_cache != nullptr)) ||
-        (k_cache && ((ld_cache & 7) || !aligned16(k_cache) || !aligned16(v_cache))) || (ldo & 7) || !aligned16(cos_table) || !aligned16(sin_table))
-        return fail(LMI_EINVAL, "lmi_rmsnorm_rope_lo4: bad argument");
+    if (const int rc = rope_entry_check("lmi_rmsnorm_rope_lo4", cos_table, sin_table, k_cache, v_cache, ld_cache, n_q_heads, n_kv_heads, head_dim, ldo)) return rc;
     GemmExtras x;
     x.rowsq_in = rowsq_in; x.rowsq_parts = rowsq_parts; x.norm_dim = K; x.norm_eps = norm_eps;
     x.rope_cos = cos_table; x.rope_sin = sin_table; x.k_cache = k_cache; x.v_cache = v_cache; x.ld_cache = ld_cache; x.cache_pos0 = cache_pos0;

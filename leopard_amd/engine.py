@@ -245,6 +245,12 @@ class LeopardEngine:
         self._encode_graphs: Dict[tuple, tuple] = {}   # (ViT-input count, stream) -> (graph, static in, static out)
         self._private_scratch = False  # True while an encode graph is warmed up / captured: _carve hands out fresh allocations the graph owns
         self.fuse_norm_rope = True     # Llama layers: RMSNorm + RoPE + KV append inside the GEMM epilogues (lmi_rmsnorm_rope / lmi_gemm_ex)
+        # Last Llama / Mistral layer of a single-sequence prefill: "read" = everything after its k | v projection runs only on a
+        # trailing row window that holds the row whose logits are read (nothing else of that layer is read afterwards: K / V need every row
+        # of the layer's INPUT, the rest only feeds the head); "all" = every row (A/B; LMI_LAST_LAYER_ROWS).  Same bits either way.
+        self.last_layer_rows = os.environ.get("LMI_LAST_LAYER_ROWS", "read")
+        if self.last_layer_rows not in ("read", "all"):
+            raise ValueError(f"LMI_LAST_LAYER_ROWS must be 'read' or 'all', not {self.last_layer_rows!r}")
         self.suppress_tokens = None    # optional int64 device tensor of token ids that greedy decoding may never emit (HF bad_words_ids)
         self.trace = None              # optional callable(name, fp32 residual stream) after the embeddings / every layer (tests)
         # Split-operand precision mode: every A operand of every ViT / LLM layer linear is handed over as a hi + lo pair of
@@ -290,6 +296,8 @@ class LeopardEngine:
         self._inv_freq = llama3_inv_freq(tc.head_dim, tc.rope_theta, tc.rope_scaling).to(self.device)
         self._geom_cache: Dict[tuple, tuple] = {}      # seq_lens -> (cu, cos, sin, last_rows) device tensors
         self._vit_cu_cache: Dict[int, torch.Tensor] = {}
+        self._window_sel: Dict[tuple, tuple] = {}         # (row_sel pointer, w0) -> the lo4 selection tables of that row window (_window_selection)
+        self._window_cu: Dict[tuple, torch.Tensor] = {}   # (S, w0) -> cu_seqlens_q of the last layer's row window (_last_layer_window)
         self._split_w = None           # [W | W] weight copies of the split-operand mode (_split_weights)
         self._gen_cache = None         # the KV cache generate() reuses (_generation_cache)
         self._stream_cache = None      # the KV cache generate_stream prefills a newcomer into before its rows move to a slot
@@ -806,10 +814,12 @@ class LeopardEngine:
                 self.trace(f"vit.{li}", x)
 
     def _llm_layers_lo4(self, x, cache, cu, cos, sin, max_len, seq_lens=None, all_rows=False, extra_rows=None, prefix=None, cache_pos0=0,
-                        cu_k=None):
+                        cu_k=None, last_only=False):
         """The Llama / Mistral layers with the low-bit correction phase, on the FUSED schedule of the fast path: the RMSNorms ride in the GEMM
         epilogues (the producers o_proj / down_proj also write the fp4 image of the residual of T(x gamma)), q|k|v + RoPE + KV append is one
-        launch, gate/up's SwiGLU epilogue writes down_proj's operand pair, the attention kernel o_proj's: no launch is added to the fast schedule."""
+        launch, gate/up's SwiGLU epilogue writes down_proj's operand pair, the attention kernel o_proj's: no launch is added to the fast schedule.
+        ``last_only``: as in _llm_layers_fast; the window also holds every selected row, so the selection tables are sliced with the rows."""
+        from .ops import Lo4Weight
         ops, W, tc = self.ops, self.W, self.cfg.text_config
         S, D = x.shape
         (H, KV), hd = self._llm_heads(), tc.head_dim
@@ -828,9 +838,28 @@ class LeopardEngine:
         sq_a, sq_b = self._empty(S, parts, dtype=torch.float32), self._empty(S, parts, dtype=torch.float32)
         scale = hd ** -0.5
         n_layers = len(W.llm_layers)
+        win = None
+        if last_only and prefix is None and cu_k is None and sel is not None:      # (sel None = every row selected: the window would have to hold them all)
+            assert len(sel[2]) == 1 and int(sel[2][0, 1]) == S        # one sequence, no scored rows: the selection is its tail, one range
+            win = self._last_layer_window(S, int(sel[2][0, 0]))
         for i, (L, (qkv4, o4, gu4, down4)) in enumerate(zip(W.llm_layers, self._lo4_weights("llm"))):
             if i == 0:
                 ops.norm_lo4(x, L.in_norm, None, h, tc.rms_norm_eps)
+            if win is not None and i == n_layers - 1:
+                w0 = win[0]
+                wq, wkv = self._qkv_weight_parts(L.qkv_w_rope, qw)
+                q4, kv4 = Lo4Weight(qkv4.img[:qw], qkv4.sc[:qw]), Lo4Weight(qkv4.img[qw:], qkv4.sc[qw:])
+                wsel = self._window_selection(sel, w0)
+                hw, attw, guw = (a.rows_from(w0, wsel) for a in (h, att, gu))
+                ops.rmsnorm_rope_lo4(h, wkv, kv4, qkv[:, qw:], None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin,
+                                     cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0, 0, KV, hd)
+                ops.rmsnorm_rope_lo4(hw, wq, q4, qkv[w0:, :qw], None if i == 0 else sq_b[w0:], tc.rms_norm_eps, cos[w0:], sin[w0:],
+                                     None, None, 0, H, 0, hd)
+                self._attend(i, qkv, attw, cu, max_len, cache, None, None, window=win)
+                ops.gemm_lo4(attw, L.o_w, o4, x[w0:], epilogue=_lib.EPI_RESIDUAL, norm_out=hw.hi, norm_gamma=L.post_norm, rowsq_out=sq_a[w0:], out4=hw)
+                ops.gemm_lo4(hw, L.gu_w, gu4, guw.hi, epilogue=_lib.EPI_SWIGLU, rowsq_in=sq_a[w0:], norm_dim=D, norm_eps=tc.rms_norm_eps, out4=guw)
+                ops.gemm_lo4(guw, L.down_w, down4, x[w0:], epilogue=_lib.EPI_RESIDUAL)
+                break
             ops.rmsnorm_rope_lo4(h, L.qkv_w_rope, qkv4, qkv, None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin,
                                  cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0, H, KV, hd)
             self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)
@@ -953,7 +982,9 @@ class LeopardEngine:
                     all_logits: bool = False, score_rows: Optional[np.ndarray] = None):
         """x: fp32 [sum(seq_lens), D] residual stream (updated in place).  Returns (logits_last [n_seq, V],
         logits_all or None).  ``cache`` (single sequence only) receives rotated K and V.  ``score_rows`` (score / score_batch): the packed
-        rows whose logits are read — the lo4 schedule corrects them as well — and no head runs here: returns (None, None)."""
+        rows whose logits are read — the lo4 schedule corrects them as well — and no head runs here: returns (None, None).
+        One sequence whose last-row logits are all that is read (``last_layer_rows`` = "read"): the last layer updates only a trailing window
+        of ``x``; the rows before it keep that layer's input."""
         S = x.shape[0]
         cu, cos, sin, last_rows, cu_list = self.sequence_geometry(seq_lens)
         assert cu_list[-1] == S
@@ -962,49 +993,101 @@ class LeopardEngine:
             assert cache.length == 0 and cache.capacity >= S
         max_len = max(int(l) for l in seq_lens)
         self.last_lo4_ranges = None
+        # nothing but the last row's logits (and the KV cache) leaves this call: the last layer may skip the other rows (_last_layer_window)
+        last_only = (self.last_layer_rows == "read" and len(seq_lens) == 1 and not all_logits and score_rows is None and self.trace is None
+                     and self._rec is None)
         if self.trace:
             self.trace("llm.embed", x)
         if self.fp8 is not None:
             self._llm_layers_fp8(x, cache, cu, cos, sin, max_len, seq_lens)
         elif self.lo4 and self.tp_size == 1:
-            self._llm_layers_lo4(x, cache, cu, cos, sin, max_len, seq_lens, all_rows=all_logits, extra_rows=score_rows)
+            self._llm_layers_lo4(x, cache, cu, cos, sin, max_len, seq_lens, all_rows=all_logits, extra_rows=score_rows, last_only=last_only)
         elif self.split_operands and self.tp_size == 1:
             self._llm_layers_split(x, cache, cu, cos, sin, max_len)
         else:
-            self._llm_layers_fast(x, cache, cu, cos, sin, max_len)
+            self._llm_layers_fast(x, cache, cu, cos, sin, max_len, last_only=last_only)
         if cache is not None:
             cache.length = S
         return (None, None) if score_rows is not None else self._lm_head(x, last_rows, all_logits)
 
-    def _attend(self, i, qkv, att, cu, max_len, cache, prefix, cu_k):
+    def _attend(self, i, qkv, att, cu, max_len, cache, prefix, cu_k, window=None):
         """The attention launch of layer i over the packed q|k|v rows.  ``att``: the 16-bit output rows, or the Lo4Act of the lo4 schedule.
         Default: causal self-attention of the packed sequences.  ``prefix`` (extend): every sequence's keys are [the P cached rows of
         ``prefix`` ; its own rows] — the two-range launch, the prefix read in place.  ``cu_k`` (append): the keys are the rows of ``cache``
-        itself, which the q|k|v epilogue has just extended."""
+        itself, which the q|k|v epilogue has just extended.  ``window`` = (w0, cu_w) (_last_layer_window; one sequence): the queries are
+        the rows w0.. of ``qkv`` (``att``: their output rows), the keys every row — cu_q = cu_w != cu_k = cu, bottom-right causal."""
         ops, tc = self.ops, self.cfg.text_config
         (H, KV), hd = self._llm_heads(), tc.head_dim
         qw, kw = H * hd, KV * hd
         q, k, v = qkv[:, :qw], qkv[:, qw:qw + kw], qkv[:, qw + kw:]
         lo4 = not isinstance(att, torch.Tensor)
         if prefix is not None:
+            assert window is None
             P = prefix.length
             if lo4:
                 ops.attention_prefix_lo4(q, k, v, prefix.k[i][:P], prefix.v[i][:P], P, att, cu, max_len, H, KV, hd, hd ** -0.5)
             else:
                 ops.attention_prefix(q, k, v, prefix.k[i][:P], prefix.v[i][:P], P, att, cu, max_len, H, KV, hd, hd ** -0.5)
             return
-        if cu_k is not None:
+        # (queries, cu_seqlens_q, cu_seqlens_k, longest query sequence) per mode; k / v: the packed rows, or the cache (append)
+        if window is not None:
+            assert cu_k is None
+            w0, cu_w = window
+            q, cu_q, cu_keys, max_q = q[w0:], cu_w, cu, max_len - w0
+        elif cu_k is not None:
             k, v = cache.k[i], cache.v[i]
-        if lo4:
-            ops.attention_lo4(q, k, v, att, cu, cu if cu_k is None else cu_k, max_len, H, KV, hd, hd ** -0.5, True, window=tc.sliding_window or 0)
+            cu_q, cu_keys, max_q = cu, cu_k, max_len
         else:
-            ops.attention(q, k, v, att, cu, cu if cu_k is None else cu_k, max_len, H, KV, hd, hd ** -0.5, True, self.use_tr,
-                          window=tc.sliding_window or 0)
+            cu_q, cu_keys, max_q = cu, cu, max_len
+        if lo4:
+            ops.attention_lo4(q, k, v, att, cu_q, cu_keys, max_q, H, KV, hd, hd ** -0.5, True, window=tc.sliding_window or 0)
+        else:
+            ops.attention(q, k, v, att, cu_q, cu_keys, max_q, H, KV, hd, hd ** -0.5, True, self.use_tr, window=tc.sliding_window or 0)
 
-    def _llm_layers_fast(self, x, cache, cu, cos, sin, max_len, prefix=None, cache_pos0=0, cu_k=None):
+    def _last_layer_window(self, S: int, first_needed: int):
+        """(w0, cu_w) of the trailing row window [w0, S) the last layer of a one-sequence prefill runs on after its k | v projection, or None
+        when that is the whole sequence.  ``first_needed``: the first row that must be in it (the read row; under lo4 the first selected
+        row).  w0 is a multiple of ATT_BQ = 128 rows from the sequence start: the attention decides its deferred rescale per 32-row wave of a
+        128-row query block, so a row's bits depend on its wave-mates — an aligned window keeps the blocks of the full launch — and the
+        64-row units of the lo4 selection can be sliced.  cu_w: the window's cu_seqlens_q (cached: building one is a host-to-device copy)."""
+        w0 = min(int(first_needed), S - 1) // 128 * 128
+        if w0 <= 0:
+            return None
+        cu_w = self._window_cu.get((S, w0))
+        if cu_w is None:
+            if len(self._window_cu) >= 64:                       # one entry per sequence length served: bounded, oldest out first
+                self._window_cu.pop(next(iter(self._window_cu)))
+            cu_w = self._window_cu[(S, w0)] = torch.tensor([0, S - w0], dtype=torch.int32, device=self.device)
+        return w0, cu_w
+
+    def _window_selection(self, sel: tuple, w0: int) -> tuple:
+        """The selection tables of _lo4_selection for the rows w0.. (w0 % 64 == 0; every selected row at or after w0): row_sel / unit_sel
+        views and the host ranges relative to w0.  Cached beside the tables they are cut from (which the views keep alive)."""
+        key = (sel[0].data_ptr(), w0)
+        hit = self._window_sel.get(key)
+        if hit is None:
+            if len(self._window_sel) >= 64:
+                self._window_sel.pop(next(iter(self._window_sel)))
+            hit = self._window_sel[key] = (sel[0][w0:], sel[1][w0 // 64:], np.ascontiguousarray(sel[2] - w0, dtype=np.int32))
+        return hit
+
+    @staticmethod
+    def _qkv_weight_parts(w_rope: torch.Tensor, q_rows: int):
+        """(q rows, k | v rows) of a rope-ordered q|k|v weight as views: row slices of the nn.Linear layout, and of the packed order too (its
+        16-row groups are contiguous; the layout mark is a property of the tensor object, so the views get their own)."""
+        from .weights import is_packed, mark_packed
+        wq, wkv = w_rope[:q_rows], w_rope[q_rows:]
+        if is_packed(w_rope):
+            assert q_rows % 16 == 0
+            mark_packed(wq), mark_packed(wkv)
+        return wq, wkv
+
+    def _llm_layers_fast(self, x, cache, cu, cos, sin, max_len, prefix=None, cache_pos0=0, cu_k=None, last_only=False):
         """The Llama / Mistral layers of the fast schedule, on the caller-owned workspace: fused (the norms and the RoPE ride in the GEMM
         epilogues) where the shapes allow it, launch by launch otherwise (also the tensor-parallel packed prefill and the calibration pass).
-        ``prefix`` / ``cache_pos0`` / ``cu_k``: continuing from cached rows (extend / append; _attend)."""
+        ``prefix`` / ``cache_pos0`` / ``cu_k``: continuing from cached rows (extend / append; _attend).  ``last_only`` (llm_prefill; fused
+        schedule): only the last row of the one sequence is read afterwards — the last layer projects k | v for every row (the cache needs
+        them) and runs q, the attention, o_proj, gate/up and down_proj on the rows of _last_layer_window alone."""
         ops, W, tc = self.ops, self.W, self.cfg.text_config
         S, D = x.shape
         (H, KV), hd = self._llm_heads(), tc.head_dim
@@ -1024,9 +1107,22 @@ class LeopardEngine:
         rec = self._rec
         if fused:
             n_layers = len(W.llm_layers)                            # sq_a: partials feeding gate/up; sq_b: feeding the next layer's qkv
+            win = self._last_layer_window(S, S - 1) if last_only and prefix is None and cu_k is None else None
             for i, L in enumerate(W.llm_layers):
                 if i == 0:
                     ops.rmsnorm(x, L.in_norm, h, tc.rms_norm_eps)
+                if win is not None and i == n_layers - 1:
+                    w0 = win[0]
+                    wq, wkv = self._qkv_weight_parts(L.qkv_w_rope, qw)
+                    ops.rmsnorm_rope(h, wkv, qkv[:, qw:], None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin,
+                                     cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0, 0, KV, hd)
+                    ops.rmsnorm_rope(h[w0:], wq, qkv[w0:, :qw], None if i == 0 else sq_b[w0:], tc.rms_norm_eps, cos[w0:], sin[w0:],
+                                     None, None, 0, H, 0, hd)
+                    self._attend(i, qkv, att[w0:], cu, max_len, cache, None, None, window=win)
+                    ops.gemm_ex(att[w0:], L.o_w, x[w0:], epilogue=_lib.EPI_RESIDUAL, norm_out=h[w0:], norm_gamma=L.post_norm, rowsq_out=sq_a[w0:])
+                    ops.gemm_ex(h[w0:], L.gu_w, gu[w0:], epilogue=_lib.EPI_SWIGLU, rowsq_in=sq_a[w0:], norm_dim=D, norm_eps=tc.rms_norm_eps)
+                    ops.gemm(gu[w0:], L.down_w, x[w0:], epilogue=_lib.EPI_RESIDUAL)
+                    break
                 ops.rmsnorm_rope(h, L.qkv_w_rope, qkv, None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin,
                                  cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0, H, KV, hd)
                 self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)

@@ -70,6 +70,15 @@ class Lo4Act:
             assert act.row_sel.dtype == torch.uint8 and act.row_sel.numel() == M and act.unit_sel.numel() == (M + 63) // 64
         return act
 
+    def rows_from(self, row0: int, sel: Optional[tuple] = None) -> "Lo4Act":
+        """The operand pair of the rows row0.. (views); ``sel``: their own selection tables (row_sel [M - row0], unit_sel — row0 % 64 == 0 —
+        and the host ranges relative to row0) when the pass has a row selection."""
+        assert (self.row_sel is None) == (sel is None) and (sel is None or row0 % 64 == 0)
+        act = Lo4Act(self.hi[row0:], self.img[row0:], self.sc[row0:])
+        if sel is not None:
+            act.row_sel, act.unit_sel, act.sel_ranges = sel
+        return act
+
 
 def lo4_packed_act(M: int, K: int, dtype, device) -> Lo4Act:
     """A Lo4Act whose image and scales are column ranges of ONE row-major uint8 buffer ``buf`` [M, K4 / 2 + K4 / 32 (+ pad to 16)]: a

@@ -5,7 +5,9 @@
 
 Builds the engine once (bench.py's C3 sample), then alternates the variants round by round (variant x round, so that clock /
 temperature drift hits every arm alike); each measurement = `steps` prefill steps between two device synchronisations.  A variant is
-`name:key=value,key=value` over lmi_set_option keys (or `eng.<attribute>=0|1` for engine switches such as eng.fp8_fused); every key any variant sets is reset to its default before each arm.  Prints the
+`name:key=value,key=value` over lmi_set_option keys (or `eng.<attribute>=0|1` for engine switches such as eng.fp8_fused;
+`eng.last_layer_rows=0|1` = the last Llama layer on every row ("all") | on the rows whose logits are read ("read", the default)); every key any
+variant sets is reset to its default before each arm.  Prints the
 per-round ms per step and the median per variant, and checks that every arm's last-position logits equal the first arm's within 2e-2
 (the options are speed-only; identical kernels give identical bits, variants that change the summation order do not)."""
 import argparse
@@ -74,6 +76,8 @@ def main():
                 eng.pack_vit_weights(bool(kv.get(k, 0)))
             elif k == "eng.llm_packed":                   # one copy of the LLM weights (packed order) vs the nn.Linear layout
                 eng.pack_llm_weights() if kv.get(k, 1) else eng.unpack_llm_weights()
+            elif k == "eng.last_layer_rows":              # last Llama layer: the read rows' window (default) vs every row
+                eng.last_layer_rows = "read" if kv.get(k, 1) else "all"
             elif k.startswith("eng."):
                 setattr(eng, k[4:], bool(kv.get(k, 1)))
             else:
