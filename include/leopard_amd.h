@@ -68,6 +68,8 @@ int lmi_abi_version(void);
  *   "skinny.coalesce"  lmi_gemm_skinny* on nn.Linear-layout weights: 1 = coalescing lane order + ds_bpermute (default), 0 = MFMA lane order
  * Unknown keys and out-of-range values return LMI_EINVAL. */
 int lmi_set_option(const char* key, int value);
+/* The current value of a knob of lmi_set_option (a caller that changes one for a while reads it first and puts it back). */
+int lmi_get_option(const char* key, int* value);
 
 /* Diagnostics (tools/overlap_probe.py): 16-byte grid-stride copy on exactly n_workgroups workgroups of 256 threads, no LDS — a
  * stand-in for a collective's transport kernel when measuring what runs beside the GEMMs.  Not used by the product path. */

@@ -32,6 +32,7 @@ class Lo4Desc(C.Structure):
 SIGNATURES = {
     "lmi_abi_version": [],
     "lmi_set_option": [C.c_char_p, _I],
+    "lmi_get_option": [C.c_char_p, C.POINTER(C.c_int)],
     "lmi_fill_synthetic": [_P, C.c_int64, C.c_uint32, _I, _I, _P],
     "lmi_preprocess_tiles": [_P, _I, _P, _I, _I, _I, _I, _I, _P],
     "lmi_preprocess_images": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P],

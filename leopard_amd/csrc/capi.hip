@@ -678,6 +678,20 @@ int lmi_set_option(const char* key, int value) {
     return fail(LMI_EINVAL, "lmi_set_option: unknown key %s", key);
 }
 
+int lmi_get_option(const char* key, int* value) {
+    if (!key || !value) return fail(LMI_EINVAL, "lmi_get_option: null pointer");
+    if (!strcmp(key, "gemm.sel_ragged_last")) { *value = g_sel_keep_ragged_last; return LMI_OK; }
+    struct { const char* key; std::atomic<int>* var; } opts[] = {
+        {"gemm.config", &g_gemm_cfg}, {"gemm.group_m", &g_gemm_group_m}, {"gemm.order", &g_gemm_order}, {"gemm.auto_small", &g_gemm_auto_small},
+        {"gemm.mid_m", &g_gemm_mid_m}, {"gemm.wide", &g_gemm_wide}, {"gemm.short_k", &g_gemm_short}, {"gemm.narrow_n", &g_gemm_narrow},
+        {"gemm.small", &g_gemm_small}, {"skinny.coalesce", &g_skinny_coalesce}, {"attn.dma", &g_attn_dma}, {"attn.rows64", &g_attn_rows64},
+        {"attn.rows64_min", &g_attn_rows64_min}, {"attn.stream_kv", &g_attn_stream_kv}, {"gemv.plan", &g_gemv_plan},
+        {"attn.gqa_pack", &g_attn_gqa_pack}, {"attn.decode_split_tiles", &g_attn_split_tiles}, {"attn.lds_pad", &g_attn_lds_pad}};
+    for (auto& o : opts)
+        if (!strcmp(key, o.key)) { *value = o.var->load(); return LMI_OK; }
+    return fail(LMI_EINVAL, "lmi_get_option: unknown key %s", key);
+}
+
 int lmi_debug_copy(const void* src, void* dst, int64_t bytes, int n_workgroups, void* stream) {
     if (!src || !dst || bytes < 0 || (bytes & 15) || n_workgroups <= 0 || !aligned16(src) || !aligned16(dst))
         return fail(LMI_EINVAL, "lmi_debug_copy: bad argument (bytes %% 16 == 0, 16-byte aligned pointers, n_workgroups > 0)");

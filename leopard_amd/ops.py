@@ -119,6 +119,11 @@ class Ops:
     def set_option(self, key: str, value: int):
         self._check(self.lib.lmi_set_option(key.encode(), int(value)))
 
+    def get_option(self, key: str) -> int:
+        value = C.c_int(0)
+        self._check(self.lib.lmi_get_option(key.encode(), C.byref(value)))
+        return value.value
+
     # ------------------------------------------------------------------------------------------
     def fill_synthetic(self, out: torch.Tensor, seed: int, kind: int):
         assert out.is_contiguous()

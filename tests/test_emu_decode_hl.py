@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from leopard_amd.weights import interleave_gate_up, rope_permute_rows, skinny_pack
+from tests import decode_hl_ref as R
 from tests.emu_util import emu_ops
 
 
@@ -155,6 +156,39 @@ def test_attention_decode_hl_writes_the_output_rows_as_pairs(ops):
     assert e_two < 0.8 * e_one, (e_two, e_one)                            # what is left is the kernel's own arithmetic: P handed to the P.V MFMA in 16 bits
     lo = two[B:2 * B].float()
     assert (lo.abs() <= 2.0 ** -11 * two[:B].float().abs() + 1e-7).all() and lo.abs().max() > 0      # a rounding residual: at most half an ulp of its hi row
+
+
+# ---- the exact-integer cases of tests/test_gpu_decode_hl.py (tests/decode_hl_ref.py: fp32 sums that are exact in any order, so the result must
+# equal the fp64 reference bit for bit), at the two short K: one k-step with seven idle waves, and 9 steps spread unevenly over the 8 waves
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("K", [128, 1152])
+@pytest.mark.parametrize("M", [1, 3, 8])
+def test_gemm_skinny_hl_exact_integer_inputs(ops, dtype, K, M):
+    R.check_gemm_hl_exact(ops, "cpu", dtype, M, K)
+    R.check_swiglu_hl(ops, "cpu", dtype, M, K)
+    R.check_producer_hl(ops, "cpu", dtype, M, K)
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("M", [1, 3, 8])
+def test_gemm_skinny_hl_swiglu_column_mapping(ops, dtype, M):
+    R.check_swiglu_hl_column_mapping(ops, "cpu", dtype, M)
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("P", [64, 256])                                 # row-square partials: K = norm_dim = 1024, 4096
+@pytest.mark.parametrize("M", [1, 3, 8])
+def test_gemm_skinny_hl_folded_norm_consumer_exact_integer_inputs(ops, dtype, P, M):
+    R.check_consumer_hl(ops, "cpu", dtype, M, P)
+
+
+@pytest.mark.parametrize("folded", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("H,KV", [(4, 1), (8, 2)])
+@pytest.mark.parametrize("M", [1, 3, 8])
+def test_rope_qkv_skinny_hl_exact_integer_inputs(ops, dtype, H, KV, M, folded):
+    for K in (128, 1152):
+        R.check_rope_qkv_hl(ops, "cpu", dtype, M, K, H, KV, folded)
 
 
 def test_engine_decode_precision_mode():

@@ -55,6 +55,44 @@ def test_abi_exports_every_declared_symbol(ops):
         pytest.skip("libleopard_amd.so not built (run `make`)")
 
 
+def _option_keys():
+    """Every key lmi_set_option compares against in csrc/capi.hip (string literals of the form "group.name" in its body)."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "leopard_amd", "csrc", "capi.hip")).read()
+    body = src[src.index("int lmi_set_option("):src.index("int lmi_get_option(")]
+    return sorted(set(re.findall(r'"([a-z0-9_]+\.[a-z0-9_]+)"', body)))
+
+
+def test_get_option_reads_back_every_key_of_set_option(ops):
+    """lmi_get_option knows every key lmi_set_option knows (the two keep separate tables: a knob added to one only fails here), returns
+    what was set, and rejects an unknown key and a null pointer with LMI_EINVAL."""
+    import ctypes
+    keys = _option_keys()
+    assert len(keys) >= 19 and "skinny.coalesce" in keys and "attn.decode_split_tiles" in keys and "gemm.sel_ragged_last" in keys
+    for key in keys:
+        before = ops.get_option(key)
+        ops.set_option(key, before)                                        # every default is a value its setter accepts
+        assert ops.get_option(key) == before, key
+    changes = {"skinny.coalesce": 0, "attn.decode_split_tiles": 4, "gemm.config": 3, "gemm.group_m": 8, "gemm.wide": 7, "attn.rows64": 2,
+               "attn.rows64_min": 2048, "attn.lds_pad": 4096, "gemm.sel_ragged_last": 1, "attn.dma": 0}
+    for key, value in changes.items():
+        before = ops.get_option(key)
+        assert before != value, key
+        try:
+            ops.set_option(key, value)
+            assert ops.get_option(key) == value, key
+        finally:
+            ops.set_option(key, before)
+        assert ops.get_option(key) == before, key
+    value = ctypes.c_int(123)
+    assert ops.lib.lmi_get_option(b"no.such_key", ctypes.byref(value)) == -1 and value.value == 123
+    assert b"unknown key" in ops.lib.lmi_last_error()
+    assert ops.lib.lmi_get_option(b"skinny.coalesce", None) == -1
+    with pytest.raises(RuntimeError):
+        ops.get_option("no.such_key")
+
+
 def test_fill_synthetic_bit_exact(ops):
     for kind in (KIND_WEIGHT, KIND_BIAS, KIND_NORM):
         for dt in (torch.float32, torch.float16, torch.bfloat16):
