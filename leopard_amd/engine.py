@@ -553,40 +553,45 @@ class LeopardEngine:
         elif self.split_operands:
             self._vit_layers_split(x, n)
         elif self.lo4 and lo4_tiles is not None and any(lo4_tiles):
-            self._vit_layers_lo4(x, n, lo4_tiles)
+            self._vit_layers(x, self._vit_cu_cache[n], T, self._vit_operands_lo4(M, lo4_tiles), self._lo4_weights("vit"), trace=self.trace)
         else:
-            self._vit_layers_fast(x, n)
+            self._vit_layers(x, self._vit_cu_cache[n], T, self._vit_operands_fast(M), rec=self._rec, trace=self.trace)
         out = self._empty(M, D)                 # a result, not scratch: the caller may hold it across later passes that reuse the workspace
         ops.layernorm(x, W.post_ln_w, W.post_ln_b, out, vc.layer_norm_eps)
         return out
 
-    def _vit_layers_fast(self, x: torch.Tensor, n: int) -> None:
-        """The SigLIP layers of the fast schedule (one rounding per operand hand-over), on the caller-owned workspace.  Like its siblings
-        below: updates the fp32 stream ``x`` in place."""
-        ops, W, vc = self.ops, self.W, self.cfg.vision_config
-        T, D, H, hd = vc.num_patches, vc.hidden_size, vc.num_attention_heads, vc.head_dim
-        M = n * T
-        cu = self._vit_cu_cache[n]
+    def _vit_operands_fast(self, M: int):
+        """(h, qkv, att, ff) of the fast SigLIP layers: 16-bit tensors on the caller-owned workspace."""
+        W, D = self.W, self.cfg.vision_config.hidden_size
         qkv_w = W.vit_layers[0].qkv_w.shape[0] if W.vit_layers else 3 * D
-        total, offs = ops.vit_workspace(M, D, qkv_w, W.vit_ff, self.dtype)
-        h, qkv, att, ff = self._carve("vit", total, offs, [(M, D, self.dtype), (M, qkv_w, self.dtype), (M, D, self.dtype), (M, W.vit_ff, self.dtype)])
+        total, offs = self.ops.vit_workspace(M, D, qkv_w, W.vit_ff, self.dtype)
+        return self._carve("vit", total, offs, [(M, D, self.dtype), (M, qkv_w, self.dtype), (M, D, self.dtype), (M, W.vit_ff, self.dtype)])
+
+    def _vit_layers(self, x: torch.Tensor, cu: torch.Tensor, max_len: int, operands, w4s=None, rec=None, trace=None) -> None:
+        """The SigLIP layers of the fast and of the lo4 schedule over the packed sequences ``cu``; like its siblings below, updates the fp32
+        stream ``x`` in place.  ``operands`` = (h, qkv, att, ff) choose the schedule (ops.linear): 16-bit tensors = fast, one rounding per
+        operand hand-over; h / att / ff as Lo4Acts with ``w4s`` (_lo4_weights("vit")) = the low-bit correction phase: the LayerNorms and fc1's
+        GELU epilogue hand over T(y) + the fp4 image of y - T(y) directly, and so does the attention kernel (lmi_attn_varlen_fwd_lo4: every
+        head padded to 96 slots in the image, out_proj's weight image laid out to match).  q / k / v and the attention arithmetic stay 16-bit.
+        ``rec`` / ``trace``: the calibration and trace hooks of the caller, if it has any."""
+        ops, W, vc = self.ops, self.W, self.cfg.vision_config
+        D, H, hd = vc.hidden_size, vc.num_attention_heads, vc.head_dim
+        h, qkv, att, ff = operands
         scale = hd ** -0.5
-        rec = self._rec
-        for li, L in enumerate(W.vit_layers):
-            ops.layernorm(x, L.ln1_w, L.ln1_b, h, vc.layer_norm_eps)
+        for li, (L, (qkv4, o4, fc14, fc24)) in enumerate(zip(W.vit_layers, w4s or [(None,) * 4] * len(W.vit_layers))):
+            ops.norm(x, L.ln1_w, L.ln1_b, h, vc.layer_norm_eps)
             rec and rec(("vit", li, "h1"), h)
-            ops.gemm(h, L.qkv_w, qkv, bias=L.qkv_b)
-            ops.attention(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], att, cu, cu, T, H, H, hd, scale, False,
-                          self.use_tr)
+            ops.linear(h, L.qkv_w, qkv, qkv4, bias=L.qkv_b)
+            ops.attend(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], att, cu, cu, max_len, H, H, hd, scale, False, self.use_tr)
             rec and rec(("vit", li, "att"), att)
-            ops.gemm(att, L.o_w, x, bias=L.o_b, epilogue=_lib.EPI_RESIDUAL)
-            ops.layernorm(x, L.ln2_w, L.ln2_b, h, vc.layer_norm_eps)
+            ops.linear(att, L.o_w, x, o4, bias=L.o_b, epilogue=_lib.EPI_RESIDUAL)
+            ops.norm(x, L.ln2_w, L.ln2_b, h, vc.layer_norm_eps)
             rec and rec(("vit", li, "h2"), h)
-            ops.gemm(h, L.fc1_w, ff, bias=L.fc1_b, act=_lib.ACT_GELU_TANH)
+            ops.linear(h, L.fc1_w, ff, fc14, bias=L.fc1_b, act=_lib.ACT_GELU_TANH)
             rec and rec(("vit", li, "ff"), ff)
-            ops.gemm(ff, L.fc2_w, x, bias=L.fc2_b, epilogue=_lib.EPI_RESIDUAL)
-            if self.trace:
-                self.trace(f"vit.{li}", x)
+            ops.linear(ff, L.fc2_w, x, fc24, bias=L.fc2_b, epilogue=_lib.EPI_RESIDUAL)
+            if trace:
+                trace(f"vit.{li}", x)
 
     def _vit_layers_fp8(self, x: torch.Tensor, n: int) -> None:
         """The SigLIP layers with fp8 linears (leopard_amd.fp8): LayerNorm -> fp8 operand in one launch, fc1's GELU epilogue
@@ -783,13 +788,11 @@ class LeopardEngine:
         from .ops import Lo4Act, lo4_head_k4
         return Lo4Act.empty(rows, width, self.dtype, self.device, k4=lo4_head_k4(*heads) if heads else None, sel=sel)
 
-    def _vit_layers_lo4(self, x: torch.Tensor, n: int, flags: Optional[Sequence[bool]] = None) -> None:
-        """The SigLIP layers with the low-bit correction phase: the LayerNorms and fc1's GELU epilogue hand over T(y) + the fp4 image of
-        y - T(y) directly, and so does the attention kernel (lmi_attn_varlen_fwd_lo4: every head padded to 96 slots in the image, out_proj's
-        weight image laid out to match).  q / k / v and the attention arithmetic stay 16-bit."""
-        ops, W, vc = self.ops, self.W, self.cfg.vision_config
-        T, D, H, hd = vc.num_patches, vc.hidden_size, vc.num_attention_heads, vc.head_dim
-        M = n * T
+    def _vit_operands_lo4(self, M: int, flags: Optional[Sequence[bool]] = None):
+        """(h, qkv, att, ff) of the SigLIP layers with the low-bit correction phase (_vit_layers): h / att / ff as operand pairs.  ``flags``:
+        per ViT input of the tile tower, whether it is corrected (None = every row)."""
+        W, vc = self.W, self.cfg.vision_config
+        D, H, hd = vc.hidden_size, vc.num_attention_heads, vc.head_dim
         # (a packed batch whose samples differ: the row selection of the correction phase carries the per-input decision — every row of a selected
         # ViT input, none of the others: _lo4_selection with "sequences" = the inputs)
         sel = None
@@ -797,81 +800,9 @@ class LeopardEngine:
             key = ("vit", tuple(bool(f) for f in flags))
             sel = self._lo4_sel_cache.get(key)
             if sel is None:
-                sel = self._lo4_sel_cache[key] = self._selection_tables(np.repeat(np.array(flags, dtype=np.uint8), T), pinned=True)
+                sel = self._lo4_sel_cache[key] = self._selection_tables(np.repeat(np.array(flags, dtype=np.uint8), vc.num_patches), pinned=True)
         h, att, ff = self._lo4_act(M, D, sel=sel), self._lo4_act(M, D, heads=(H, hd), sel=sel), self._lo4_act(M, W.vit_ff, sel=sel)
-        qkv = self._empty(M, W.vit_layers[0].qkv_w.shape[0])
-        cu = self._vit_cu_cache[n]
-        scale = hd ** -0.5
-        for li, (L, (qkv4, o4, fc14, fc24)) in enumerate(zip(W.vit_layers, self._lo4_weights("vit"))):
-            ops.norm_lo4(x, L.ln1_w, L.ln1_b, h, vc.layer_norm_eps)
-            ops.gemm_lo4(h, L.qkv_w, qkv4, qkv, bias=L.qkv_b)
-            ops.attention_lo4(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], att, cu, cu, T, H, H, hd, scale, False)
-            ops.gemm_lo4(att, L.o_w, o4, x, bias=L.o_b, epilogue=_lib.EPI_RESIDUAL)
-            ops.norm_lo4(x, L.ln2_w, L.ln2_b, h, vc.layer_norm_eps)
-            ops.gemm_lo4(h, L.fc1_w, fc14, ff.hi, bias=L.fc1_b, act=_lib.ACT_GELU_TANH, out4=ff)
-            ops.gemm_lo4(ff, L.fc2_w, fc24, x, bias=L.fc2_b, epilogue=_lib.EPI_RESIDUAL)
-            if self.trace:
-                self.trace(f"vit.{li}", x)
-
-    def _llm_layers_lo4(self, x, cache, cu, cos, sin, max_len, seq_lens=None, all_rows=False, extra_rows=None, prefix=None, cache_pos0=0,
-                        cu_k=None, last_only=False):
-        """The Llama / Mistral layers with the low-bit correction phase, on the FUSED schedule of the fast path: the RMSNorms ride in the GEMM
-        epilogues (the producers o_proj / down_proj also write the fp4 image of the residual of T(x gamma)), q|k|v + RoPE + KV append is one
-        launch, gate/up's SwiGLU epilogue writes down_proj's operand pair, the attention kernel o_proj's: no launch is added to the fast schedule.
-        ``last_only``: as in _llm_layers_fast; the window also holds every selected row, so the selection tables are sliced with the rows."""
-        from .ops import Lo4Weight
-        ops, W, tc = self.ops, self.W, self.cfg.text_config
-        S, D = x.shape
-        (H, KV), hd = self._llm_heads(), tc.head_dim
-        qw, kw = H * hd, KV * hd
-        if not (hd == 128 and D % 256 == 0 and W.llm_layers and W.llm_layers[0].qkv_w_rope is not None):
-            raise RuntimeError("precision 'lo4' needs head_dim 128 and the rope-ordered q|k|v weights (the fused Llama / Mistral schedule)")
-        # row selection (lo4_rows): only the trailing rows of each sequence hand over residual images; the other rows' images stay zero and the
-        # tiles without a selected row skip the fp4 k-tiles (csrc/gemm.h GemmArgs::row_sel)
-        # (``all_rows``: the caller reads the logits of EVERY row — all_logits — so every row is a logits row)
-        # (``extra_rows``: packed rows whose logits are read besides the tails — score / score_batch: corrected too)
-        sel = None if all_rows else self._lo4_selection(seq_lens if seq_lens is not None else [S], extra_rows)
-        self.last_lo4_ranges = np.array([[0, S]], dtype=np.int32) if sel is None else sel[2].copy()
-        h, att, gu = self._lo4_act(S, D, sel=sel), self._lo4_act(S, qw, heads=(H, hd), sel=sel), self._lo4_act(S, W.llm_ff, sel=sel)
-        qkv = self._empty(S, qw + 2 * kw)
-        parts = (D + 63) // 64
-        sq_a, sq_b = self._empty(S, parts, dtype=torch.float32), self._empty(S, parts, dtype=torch.float32)
-        scale = hd ** -0.5
-        n_layers = len(W.llm_layers)
-        win = None
-        if last_only and prefix is None and cu_k is None and sel is not None:      # (sel None = every row selected: the window would have to hold them all)
-            assert len(sel[2]) == 1 and int(sel[2][0, 1]) == S        # one sequence, no scored rows: the selection is its tail, one range
-            win = self._last_layer_window(S, int(sel[2][0, 0]))
-        for i, (L, (qkv4, o4, gu4, down4)) in enumerate(zip(W.llm_layers, self._lo4_weights("llm"))):
-            if i == 0:
-                ops.norm_lo4(x, L.in_norm, None, h, tc.rms_norm_eps)
-            if win is not None and i == n_layers - 1:
-                w0 = win[0]
-                wq, wkv = self._qkv_weight_parts(L.qkv_w_rope, qw)
-                q4, kv4 = Lo4Weight(qkv4.img[:qw], qkv4.sc[:qw]), Lo4Weight(qkv4.img[qw:], qkv4.sc[qw:])
-                wsel = self._window_selection(sel, w0)
-                hw, attw, guw = (a.rows_from(w0, wsel) for a in (h, att, gu))
-                ops.rmsnorm_rope_lo4(h, wkv, kv4, qkv[:, qw:], None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin,
-                                     cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0, 0, KV, hd)
-                ops.rmsnorm_rope_lo4(hw, wq, q4, qkv[w0:, :qw], None if i == 0 else sq_b[w0:], tc.rms_norm_eps, cos[w0:], sin[w0:],
-                                     None, None, 0, H, 0, hd)
-                self._attend(i, qkv, attw, cu, max_len, cache, None, None, window=win)
-                ops.gemm_lo4(attw, L.o_w, o4, x[w0:], epilogue=_lib.EPI_RESIDUAL, norm_out=hw.hi, norm_gamma=L.post_norm, rowsq_out=sq_a[w0:], out4=hw)
-                ops.gemm_lo4(hw, L.gu_w, gu4, guw.hi, epilogue=_lib.EPI_SWIGLU, rowsq_in=sq_a[w0:], norm_dim=D, norm_eps=tc.rms_norm_eps, out4=guw)
-                ops.gemm_lo4(guw, L.down_w, down4, x[w0:], epilogue=_lib.EPI_RESIDUAL)
-                break
-            ops.rmsnorm_rope_lo4(h, L.qkv_w_rope, qkv4, qkv, None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin,
-                                 cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0, H, KV, hd)
-            self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)
-            ops.gemm_lo4(att, L.o_w, o4, x, epilogue=_lib.EPI_RESIDUAL, norm_out=h.hi, norm_gamma=L.post_norm, rowsq_out=sq_a, out4=h)
-            ops.gemm_lo4(h, L.gu_w, gu4, gu.hi, epilogue=_lib.EPI_SWIGLU, rowsq_in=sq_a, norm_dim=D, norm_eps=tc.rms_norm_eps, out4=gu)
-            if i + 1 < n_layers:
-                ops.gemm_lo4(gu, L.down_w, down4, x, epilogue=_lib.EPI_RESIDUAL, norm_out=h.hi, norm_gamma=W.llm_layers[i + 1].in_norm,
-                             rowsq_out=sq_b, out4=h)
-            else:
-                ops.gemm_lo4(gu, L.down_w, down4, x, epilogue=_lib.EPI_RESIDUAL)
-            if self.trace:
-                self.trace(f"llm.{i}", x)
+        return h, self._empty(M, W.vit_layers[0].qkv_w.shape[0]), att, ff
 
     def enable_fp8(self, calibration_samples, headroom: float = 2.0):
         """Switch the ViT / LLM layer linears to fp8 operands (BASELINE configs[4]): quantise the weights once, take the static
@@ -1000,12 +931,10 @@ class LeopardEngine:
             self.trace("llm.embed", x)
         if self.fp8 is not None:
             self._llm_layers_fp8(x, cache, cu, cos, sin, max_len, seq_lens)
-        elif self.lo4 and self.tp_size == 1:
-            self._llm_layers_lo4(x, cache, cu, cos, sin, max_len, seq_lens, all_rows=all_logits, extra_rows=score_rows, last_only=last_only)
-        elif self.split_operands and self.tp_size == 1:
+        elif self.split_operands and self.tp_size == 1 and not self.lo4:
             self._llm_layers_split(x, cache, cu, cos, sin, max_len)
         else:
-            self._llm_layers_fast(x, cache, cu, cos, sin, max_len, last_only=last_only)
+            self._llm_layers(x, cache, cu, cos, sin, max_len, seq_lens, all_rows=all_logits, extra_rows=score_rows, last_only=last_only)
         if cache is not None:
             cache.length = S
         return (None, None) if score_rows is not None else self._lm_head(x, last_rows, all_logits)
@@ -1020,14 +949,10 @@ class LeopardEngine:
         (H, KV), hd = self._llm_heads(), tc.head_dim
         qw, kw = H * hd, KV * hd
         q, k, v = qkv[:, :qw], qkv[:, qw:qw + kw], qkv[:, qw + kw:]
-        lo4 = not isinstance(att, torch.Tensor)
         if prefix is not None:
             assert window is None
             P = prefix.length
-            if lo4:
-                ops.attention_prefix_lo4(q, k, v, prefix.k[i][:P], prefix.v[i][:P], P, att, cu, max_len, H, KV, hd, hd ** -0.5)
-            else:
-                ops.attention_prefix(q, k, v, prefix.k[i][:P], prefix.v[i][:P], P, att, cu, max_len, H, KV, hd, hd ** -0.5)
+            ops.attend_prefix(q, k, v, prefix.k[i][:P], prefix.v[i][:P], P, att, cu, max_len, H, KV, hd, hd ** -0.5)
             return
         # (queries, cu_seqlens_q, cu_seqlens_k, longest query sequence) per mode; k / v: the packed rows, or the cache (append)
         if window is not None:
@@ -1039,10 +964,7 @@ class LeopardEngine:
             cu_q, cu_keys, max_q = cu, cu_k, max_len
         else:
             cu_q, cu_keys, max_q = cu, cu, max_len
-        if lo4:
-            ops.attention_lo4(q, k, v, att, cu_q, cu_keys, max_q, H, KV, hd, hd ** -0.5, True, window=tc.sliding_window or 0)
-        else:
-            ops.attention(q, k, v, att, cu_q, cu_keys, max_q, H, KV, hd, hd ** -0.5, True, self.use_tr, window=tc.sliding_window or 0)
+        ops.attend(q, k, v, att, cu_q, cu_keys, max_q, H, KV, hd, hd ** -0.5, True, self.use_tr, window=tc.sliding_window or 0)
 
     def _last_layer_window(self, S: int, first_needed: int):
         """(w0, cu_w) of the trailing row window [w0, S) the last layer of a one-sequence prefill runs on after its k | v projection, or None
@@ -1082,81 +1004,115 @@ class LeopardEngine:
             mark_packed(wq), mark_packed(wkv)
         return wq, wkv
 
-    def _llm_layers_fast(self, x, cache, cu, cos, sin, max_len, prefix=None, cache_pos0=0, cu_k=None, last_only=False):
-        """The Llama / Mistral layers of the fast schedule, on the caller-owned workspace: fused (the norms and the RoPE ride in the GEMM
-        epilogues) where the shapes allow it, launch by launch otherwise (also the tensor-parallel packed prefill and the calibration pass).
+    def _llm_layers(self, x, cache, cu, cos, sin, max_len, seq_lens=None, all_rows=False, extra_rows=None, prefix=None, cache_pos0=0,
+                    cu_k=None, last_only=False):
+        """The Llama / Mistral layers of the fast and of the lo4 schedule: the buffers, the row selection and the weight images are set up per
+        schedule, then ONE layer body serves both — the operands choose the entries (ops.linear; fast: 16-bit tensors on the caller-owned
+        workspace, lo4: Lo4Acts).  That body is the FUSED schedule: the RMSNorms ride in the GEMM epilogues (under lo4 the producers o_proj /
+        down_proj also write the fp4 image of the residual of T(x gamma)), q|k|v + RoPE + KV append is one launch, gate/up's SwiGLU epilogue
+        writes down_proj's operand (pair), the attention kernel o_proj's: lo4 adds no launch to the fast schedule.  Where the shapes do not
+        allow the fusion the fast schedule runs launch by launch (_llm_layers_unfused); lo4 needs it.
         ``prefix`` / ``cache_pos0`` / ``cu_k``: continuing from cached rows (extend / append; _attend).  ``last_only`` (llm_prefill; fused
         schedule): only the last row of the one sequence is read afterwards — the last layer projects k | v for every row (the cache needs
-        them) and runs q, the attention, o_proj, gate/up and down_proj on the rows of _last_layer_window alone."""
+        them) and runs q, the attention, o_proj, gate/up and down_proj on the rows of _last_layer_window alone; under lo4 the window also
+        holds every selected row, so the selection tables are sliced with the rows.  ``seq_lens`` / ``all_rows`` / ``extra_rows``: what
+        the lo4 row selection is made from (below)."""
+        from .ops import Lo4Weight, rows_from
         ops, W, tc = self.ops, self.W, self.cfg.text_config
         S, D = x.shape
         (H, KV), hd = self._llm_heads(), tc.head_dim
         qw, kw = H * hd, KV * hd
         parts = (D + 63) // 64
-        total, offs = ops.llm_prefill_workspace(S, D, H, KV, hd, W.llm_ff, self.dtype)
-        h, qkv, att, gu, sq_a, sq_b = self._carve("llm", total, offs, [(S, D, self.dtype), (S, qw + 2 * kw, self.dtype), (S, qw, self.dtype),
-                                                                         (S, W.llm_ff, self.dtype), (S, parts, torch.float32), (S, parts, torch.float32)])
-        tmp = self._empty(S, D, dtype=torch.float32) if self.tp_size > 1 else None
-        scale = hd ** -0.5
+        lo4 = self.lo4 and self.tp_size == 1
         # Fused schedule (one rank, head_dim 128): the RMSNorms and the RoPE ride in the GEMM epilogues.  Each residual GEMM
         # (o_proj, down_proj) also emits T(x * gamma_next) and per-row partial sums of squares; the GEMM that consumes them
         # (gate/up, next layer's qkv) applies rstd to its accumulator rows; the qkv GEMM rotates q / k and appends K / V to the
         # cache in its epilogue.  Only the very first norm of the stack is a launch of its own.
-        fused = (self.fuse_norm_rope and self.tp_size == 1 and hd == 128 and D % 256 == 0 and W.llm_layers
-                 and W.llm_layers[0].qkv_w_rope is not None)
-        rec = self._rec
-        if fused:
-            n_layers = len(W.llm_layers)                            # sq_a: partials feeding gate/up; sq_b: feeding the next layer's qkv
-            win = self._last_layer_window(S, S - 1) if last_only and prefix is None and cu_k is None else None
-            for i, L in enumerate(W.llm_layers):
-                if i == 0:
-                    ops.rmsnorm(x, L.in_norm, h, tc.rms_norm_eps)
-                if win is not None and i == n_layers - 1:
-                    w0 = win[0]
-                    wq, wkv = self._qkv_weight_parts(L.qkv_w_rope, qw)
-                    ops.rmsnorm_rope(h, wkv, qkv[:, qw:], None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin,
-                                     cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0, 0, KV, hd)
-                    ops.rmsnorm_rope(h[w0:], wq, qkv[w0:, :qw], None if i == 0 else sq_b[w0:], tc.rms_norm_eps, cos[w0:], sin[w0:],
-                                     None, None, 0, H, 0, hd)
-                    self._attend(i, qkv, att[w0:], cu, max_len, cache, None, None, window=win)
-                    ops.gemm_ex(att[w0:], L.o_w, x[w0:], epilogue=_lib.EPI_RESIDUAL, norm_out=h[w0:], norm_gamma=L.post_norm, rowsq_out=sq_a[w0:])
-                    ops.gemm_ex(h[w0:], L.gu_w, gu[w0:], epilogue=_lib.EPI_SWIGLU, rowsq_in=sq_a[w0:], norm_dim=D, norm_eps=tc.rms_norm_eps)
-                    ops.gemm(gu[w0:], L.down_w, x[w0:], epilogue=_lib.EPI_RESIDUAL)
-                    break
-                ops.rmsnorm_rope(h, L.qkv_w_rope, qkv, None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin,
-                                 cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0, H, KV, hd)
-                self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)
-                ops.gemm_ex(att, L.o_w, x, epilogue=_lib.EPI_RESIDUAL, norm_out=h, norm_gamma=L.post_norm, rowsq_out=sq_a)
-                ops.gemm_ex(h, L.gu_w, gu, epilogue=_lib.EPI_SWIGLU, rowsq_in=sq_a, norm_dim=D, norm_eps=tc.rms_norm_eps)
-                if i + 1 < n_layers:
-                    ops.gemm_ex(gu, L.down_w, x, epilogue=_lib.EPI_RESIDUAL, norm_out=h, norm_gamma=W.llm_layers[i + 1].in_norm,
-                                rowsq_out=sq_b)
-                else:
-                    ops.gemm(gu, L.down_w, x, epilogue=_lib.EPI_RESIDUAL)
-                if self.trace:
-                    self.trace(f"llm.{i}", x)
+        fused = (self.tp_size == 1 and hd == 128 and D % 256 == 0 and W.llm_layers and W.llm_layers[0].qkv_w_rope is not None)
+        first_needed = S - 1                                         # first row the last layer's window must hold: the read row ...
+        if lo4:
+            if not fused:
+                raise RuntimeError("precision 'lo4' needs head_dim 128 and the rope-ordered q|k|v weights (the fused Llama / Mistral schedule)")
+            # row selection (lo4_rows): only the trailing rows of each sequence hand over residual images; the other rows' images stay zero and the
+            # tiles without a selected row skip the fp4 k-tiles (csrc/gemm.h GemmArgs::row_sel)
+            # (``all_rows``: the caller reads the logits of EVERY row — all_logits — so every row is a logits row)
+            # (``extra_rows``: packed rows whose logits are read besides the tails — score / score_batch: corrected too)
+            sel = None if all_rows else self._lo4_selection(seq_lens if seq_lens is not None else [S], extra_rows)
+            self.last_lo4_ranges = np.array([[0, S]], dtype=np.int32) if sel is None else sel[2].copy()
+            h, att, gu = self._lo4_act(S, D, sel=sel), self._lo4_act(S, qw, heads=(H, hd), sel=sel), self._lo4_act(S, W.llm_ff, sel=sel)
+            qkv = self._empty(S, qw + 2 * kw)
+            sq_a, sq_b = self._empty(S, parts, dtype=torch.float32), self._empty(S, parts, dtype=torch.float32)
+            w4s = self._lo4_weights("llm")
+            first_needed = 0 if sel is None else int(sel[2][0, 0])   # ... under lo4 every selected row (sel None = all of them: no window)
+            assert not last_only or sel is None or (len(sel[2]) == 1 and int(sel[2][0, 1]) == S)   # one sequence, no scored rows: its tail, one range
         else:
-            for i, L in enumerate(W.llm_layers):
-                ops.rmsnorm(x, L.in_norm, h, tc.rms_norm_eps)
-                rec and rec(("llm", i, "h1"), h)
-                if L.qkv_w is not None:
-                    ops.gemm(h, L.qkv_w, qkv)
-                    ops.rope_qk(qkv, H, KV, hd, cos, sin, cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0)
-                else:                                    # packed weights keep the rope-ordered rows only: projection + RoPE + KV append on the normalised rows
-                    ops.rmsnorm_rope(h, L.qkv_w_rope, qkv, None, tc.rms_norm_eps, cos, sin, cache.k[i] if cache else None,
-                                     cache.v[i] if cache else None, cache_pos0, H, KV, hd)
-                if rec:                                  # operands of the fp8 attention arithmetic (rotated q / k, v)
-                    rec(("llm", i, "q"), qkv[:, :qw]); rec(("llm", i, "k"), qkv[:, qw:qw + kw]); rec(("llm", i, "v"), qkv[:, qw + kw:])
-                self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)
-                rec and rec(("llm", i, "att"), att)
-                self._row_parallel(att, L.o_w, x, tmp)
-                ops.rmsnorm(x, L.post_norm, h, tc.rms_norm_eps)
-                rec and rec(("llm", i, "h2"), h)
-                ops.gemm(h, L.gu_w, gu, epilogue=_lib.EPI_SWIGLU)
-                rec and rec(("llm", i, "gu"), gu)
-                self._row_parallel(gu, L.down_w, x, tmp)
-                if self.trace:
-                    self.trace(f"llm.{i}", x)
+            sel, w4s = None, [(None,) * 4] * len(W.llm_layers)
+            total, offs = ops.llm_prefill_workspace(S, D, H, KV, hd, W.llm_ff, self.dtype)
+            h, qkv, att, gu, sq_a, sq_b = self._carve("llm", total, offs, [(S, D, self.dtype), (S, qw + 2 * kw, self.dtype), (S, qw, self.dtype),
+                                                                             (S, W.llm_ff, self.dtype), (S, parts, torch.float32), (S, parts, torch.float32)])
+            if not (fused and self.fuse_norm_rope):
+                return self._llm_layers_unfused(x, cache, cu, cos, sin, max_len, (h, qkv, att, gu), prefix, cache_pos0, cu_k)
+        win = self._last_layer_window(S, first_needed) if last_only and prefix is None and cu_k is None else None
+        n_layers = len(W.llm_layers)                            # sq_a: partials feeding gate/up; sq_b: feeding the next layer's qkv
+        for i, (L, (qkv4, o4, gu4, down4)) in enumerate(zip(W.llm_layers, w4s)):
+            kc, vc = (cache.k[i], cache.v[i]) if cache else (None, None)
+            if i == 0:
+                ops.norm(x, L.in_norm, None, h, tc.rms_norm_eps)
+            if win is not None and i == n_layers - 1:
+                w0 = win[0]
+                wq, wkv = self._qkv_weight_parts(L.qkv_w_rope, qw)
+                q4, kv4 = (Lo4Weight(qkv4.img[:qw], qkv4.sc[:qw]), Lo4Weight(qkv4.img[qw:], qkv4.sc[qw:])) if qkv4 is not None else (None, None)
+                wsel = self._window_selection(sel, w0) if sel is not None else None
+                hw, attw, guw = (rows_from(a, w0, wsel) for a in (h, att, gu))
+                ops.qkv_rope(h, wkv, qkv[:, qw:], None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin, kc, vc, cache_pos0, 0, KV, hd, kv4)
+                ops.qkv_rope(hw, wq, qkv[w0:, :qw], None if i == 0 else sq_b[w0:], tc.rms_norm_eps, cos[w0:], sin[w0:], None, None, 0, H, 0, hd, q4)
+                self._attend(i, qkv, attw, cu, max_len, cache, None, None, window=win)
+                ops.linear(attw, L.o_w, x[w0:], o4, epilogue=_lib.EPI_RESIDUAL, norm_out=hw, norm_gamma=L.post_norm, rowsq_out=sq_a[w0:])
+                ops.linear(hw, L.gu_w, guw, gu4, epilogue=_lib.EPI_SWIGLU, rowsq_in=sq_a[w0:], norm_dim=D, norm_eps=tc.rms_norm_eps)
+                ops.linear(guw, L.down_w, x[w0:], down4, epilogue=_lib.EPI_RESIDUAL)
+                break
+            ops.qkv_rope(h, L.qkv_w_rope, qkv, None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin, kc, vc, cache_pos0, H, KV, hd, qkv4)
+            self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)
+            ops.linear(att, L.o_w, x, o4, epilogue=_lib.EPI_RESIDUAL, norm_out=h, norm_gamma=L.post_norm, rowsq_out=sq_a)
+            ops.linear(h, L.gu_w, gu, gu4, epilogue=_lib.EPI_SWIGLU, rowsq_in=sq_a, norm_dim=D, norm_eps=tc.rms_norm_eps)
+            if i + 1 < n_layers:
+                ops.linear(gu, L.down_w, x, down4, epilogue=_lib.EPI_RESIDUAL, norm_out=h, norm_gamma=W.llm_layers[i + 1].in_norm, rowsq_out=sq_b)
+            else:
+                ops.linear(gu, L.down_w, x, down4, epilogue=_lib.EPI_RESIDUAL)
+            if self.trace:
+                self.trace(f"llm.{i}", x)
+
+    def _llm_layers_unfused(self, x, cache, cu, cos, sin, max_len, bufs, prefix=None, cache_pos0=0, cu_k=None):
+        """The Llama / Mistral layers of the fast schedule launch by launch, on the workspace buffers ``bufs`` = (h, qkv, att, gu): where the
+        shapes do not allow the fused schedule, the tensor-parallel packed prefill and the calibration pass (``_rec``)."""
+        ops, W, tc = self.ops, self.W, self.cfg.text_config
+        S, D = x.shape
+        (H, KV), hd = self._llm_heads(), tc.head_dim
+        qw, kw = H * hd, KV * hd
+        h, qkv, att, gu = bufs
+        tmp = self._empty(S, D, dtype=torch.float32) if self.tp_size > 1 else None
+        rec = self._rec
+        for i, L in enumerate(W.llm_layers):
+            ops.rmsnorm(x, L.in_norm, h, tc.rms_norm_eps)
+            rec and rec(("llm", i, "h1"), h)
+            if L.qkv_w is not None:
+                ops.gemm(h, L.qkv_w, qkv)
+                ops.rope_qk(qkv, H, KV, hd, cos, sin, cache.k[i] if cache else None, cache.v[i] if cache else None, cache_pos0)
+            else:                                    # packed weights keep the rope-ordered rows only: projection + RoPE + KV append on the normalised rows
+                ops.rmsnorm_rope(h, L.qkv_w_rope, qkv, None, tc.rms_norm_eps, cos, sin, cache.k[i] if cache else None,
+                                 cache.v[i] if cache else None, cache_pos0, H, KV, hd)
+            if rec:                                  # operands of the fp8 attention arithmetic (rotated q / k, v)
+                rec(("llm", i, "q"), qkv[:, :qw]); rec(("llm", i, "k"), qkv[:, qw:qw + kw]); rec(("llm", i, "v"), qkv[:, qw + kw:])
+            self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)
+            rec and rec(("llm", i, "att"), att)
+            self._row_parallel(att, L.o_w, x, tmp)
+            ops.rmsnorm(x, L.post_norm, h, tc.rms_norm_eps)
+            rec and rec(("llm", i, "h2"), h)
+            ops.gemm(h, L.gu_w, gu, epilogue=_lib.EPI_SWIGLU)
+            rec and rec(("llm", i, "gu"), gu)
+            self._row_parallel(gu, L.down_w, x, tmp)
+            if self.trace:
+                self.trace(f"llm.{i}", x)
 
     def _llm_layers_fp8(self, x, cache, cu, cos, sin, max_len, seq_lens=None):
         """The Llama layers with fp8 linears (leopard_amd.fp8): RMSNorm -> fp8 operand in one launch, the SwiGLU epilogue of
@@ -1368,7 +1324,7 @@ class LeopardEngine:
                 ms.wait_event(e)
         pos = torch.arange(NC * Sc)
         cos, sin = self.rope_tables(pos)
-        lo4 = self.lo4
+        lo4, L4 = self.lo4, [(None,) * 4] * len(W.llm_layers)
         if lo4:
             # precision "lo4" under tensor parallelism: the rank's normalised rows are Lo4 pairs (16-bit rows + fp4 image of their rounding
             # residual + block scales; image and scales in ONE buffer so that one more all-gather moves both: + 27 % all-gather bytes), the
@@ -1393,56 +1349,39 @@ class LeopardEngine:
         cu_k = [torch.tensor([0, (c + 1) * Sc], dtype=torch.int32, device=dev) for c in range(NC)]
         scale = hd ** -0.5
         epi_part = _lib.EPI_STORE if cdt == T else _lib.EPI_STORE_F32
-        fused_rope = self.fuse_norm_rope and hd == 128 and W.llm_layers and W.llm_layers[0].qkv_w_rope is not None
+        fused_rope = lo4 or (self.fuse_norm_rope and hd == 128 and W.llm_layers and W.llm_layers[0].qkv_w_rope is not None)
+        hi = lambda a: getattr(a, "hi", a)        # the 16-bit rows of an operand of either kind
         n_layers = len(W.llm_layers)
         ev = [None] * NC
 
         def gather(c):
             """all-gather of chunk c's normalised rows (and, under lo4, of their residual images) on the comm stream."""
             to_comm()
+            comm.all_gather(hi(h_full[c]), hi(h_loc[c]), cs)
             if lo4:
-                comm.all_gather(h_full[c].hi, h_loc[c].hi, cs)
                 comm.all_gather(h_full[c].buf.view(torch.float16), h_loc[c].buf.view(torch.float16), cs)
-            else:
-                comm.all_gather(h_full[c], h_loc[c], cs)
             ev[c] = done()
 
-        def add_norm(c, delta, w):
-            if w is None:
-                ops.add_rmsnorm(xs[c], delta, None, None, tc.rms_norm_eps)
-            elif lo4:
-                ops.add_rmsnorm_lo4(xs[c], delta, w, h_loc[c], tc.rms_norm_eps)
-            else:
-                ops.add_rmsnorm(xs[c], delta, w, h_loc[c], tc.rms_norm_eps)
-        for li, L in enumerate(W.llm_layers):
-            w4 = L4[li] if lo4 else None
+        def add_norm(c, delta, w):              # (w None: the add alone, after the last layer)
+            ops.add_norm(xs[c], delta, w, None if w is None else h_loc[c], tc.rms_norm_eps)
+        for li, (L, (qkv4, o4, gu4, down4)) in enumerate(zip(W.llm_layers, L4)):
             # ---- attention half ----------------------------------------------------------------------------------------
             for c in range(NC):
                 if li == 0:
-                    if lo4:
-                        ops.norm_lo4(xs[c], L.in_norm, None, h_loc[c], tc.rms_norm_eps)
-                    else:
-                        ops.rmsnorm(xs[c], L.in_norm, h_loc[c], tc.rms_norm_eps)
+                    ops.norm(xs[c], L.in_norm, None, h_loc[c], tc.rms_norm_eps)
                 gather(c)
             for c in range(NC):
                 wait(ev[c])
                 kc, vc = cache.k[li], cache.v[li]
-                if lo4:
-                    ops.rmsnorm_rope_lo4(h_full[c], L.qkv_w_rope, w4[0], qkv, None, tc.rms_norm_eps, cos[c * Sc:(c + 1) * Sc],
-                                         sin[c * Sc:(c + 1) * Sc], kc, vc, c * Sc, H, KV, hd)
-                    ops.attention_lo4(qkv[:, :qw], kc[:(c + 1) * Sc], vc[:(c + 1) * Sc], att, cu_q, cu_k[c], Sc, H, KV, hd, scale, True,
-                                      window=tc.sliding_window or 0)
-                    ops.gemm_lo4(att, L.o_w, w4[1], part[c], epilogue=epi_part)
+                if fused_rope:
+                    ops.qkv_rope(h_full[c], L.qkv_w_rope, qkv, None, tc.rms_norm_eps, cos[c * Sc:(c + 1) * Sc], sin[c * Sc:(c + 1) * Sc],
+                                 kc, vc, c * Sc, H, KV, hd, qkv4)
                 else:
-                    if fused_rope:
-                        ops.rmsnorm_rope(h_full[c], L.qkv_w_rope, qkv, None, tc.rms_norm_eps, cos[c * Sc:(c + 1) * Sc], sin[c * Sc:(c + 1) * Sc],
-                                         kc, vc, c * Sc, H, KV, hd)
-                    else:
-                        ops.gemm(h_full[c], L.qkv_w, qkv)
-                        ops.rope_qk(qkv, H, KV, hd, cos[c * Sc:(c + 1) * Sc], sin[c * Sc:(c + 1) * Sc], kc, vc, c * Sc)
-                    ops.attention(qkv[:, :qw], kc[:(c + 1) * Sc], vc[:(c + 1) * Sc], att, cu_q, cu_k[c], Sc, H, KV, hd, scale, True,
-                                  self.use_tr, window=tc.sliding_window or 0)
-                    ops.gemm(att, L.o_w, part[c], epilogue=epi_part)
+                    ops.gemm(h_full[c], L.qkv_w, qkv)
+                    ops.rope_qk(qkv, H, KV, hd, cos[c * Sc:(c + 1) * Sc], sin[c * Sc:(c + 1) * Sc], kc, vc, c * Sc)
+                ops.attend(qkv[:, :qw], kc[:(c + 1) * Sc], vc[:(c + 1) * Sc], att, cu_q, cu_k[c], Sc, H, KV, hd, scale, True,
+                           self.use_tr, window=tc.sliding_window or 0)
+                ops.linear(att, L.o_w, part[c], o4, epilogue=epi_part)
                 to_comm()
                 comm.reduce_scatter(red[c], part[c], cs)
                 ev[c] = done()
@@ -1453,12 +1392,8 @@ class LeopardEngine:
                 gather(c)
             for c in range(NC):
                 wait(ev[c])
-                if lo4:
-                    ops.gemm_lo4(h_full[c], L.gu_w, w4[2], gu.hi, epilogue=_lib.EPI_SWIGLU, out4=gu)
-                    ops.gemm_lo4(gu, L.down_w, w4[3], part[c], epilogue=epi_part)
-                else:
-                    ops.gemm(h_full[c], L.gu_w, gu, epilogue=_lib.EPI_SWIGLU)
-                    ops.gemm(gu, L.down_w, part[c], epilogue=epi_part)
+                ops.linear(h_full[c], L.gu_w, gu, gu4, epilogue=_lib.EPI_SWIGLU)
+                ops.linear(gu, L.down_w, part[c], down4, epilogue=epi_part)
                 to_comm()
                 comm.reduce_scatter(red[c], part[c], cs)
                 ev[c] = done()
@@ -2256,10 +2191,7 @@ class LeopardEngine:
         cu, cos, sin, last_rows, _ = self._continuation_geometry(P, lens)
         self.llm_packed
         self.last_lo4_ranges = None
-        if self.lo4:
-            self._llm_layers_lo4(x, kv_out, cu, cos, sin, max(lens), lens, prefix=prefix)
-        else:
-            self._llm_layers_fast(x, kv_out, cu, cos, sin, max(lens), prefix=prefix)
+        self._llm_layers(x, kv_out, cu, cos, sin, max(lens), lens, prefix=prefix)
         if kv_out is not None:
             kv_out.length = S
         last, _ = self._lm_head(x, last_rows, False)
@@ -2287,10 +2219,7 @@ class LeopardEngine:
             cu_k = self._geom_cache[ck] = torch.tensor([0, P + n], dtype=torch.int32, device=self.device)
         self.llm_packed
         self.last_lo4_ranges = None
-        if self.lo4:
-            self._llm_layers_lo4(x, cache, cu, cos, sin, n, [n], all_rows=True, cache_pos0=P, cu_k=cu_k)
-        else:
-            self._llm_layers_fast(x, cache, cu, cos, sin, n, cache_pos0=P, cu_k=cu_k)
+        self._llm_layers(x, cache, cu, cos, sin, n, [n], all_rows=True, cache_pos0=P, cu_k=cu_k)
         cache.length = P + n
         _, logits = self._lm_head(x, last_rows, True)
         return logits

@@ -155,7 +155,7 @@ class Idefics2Engine(LeopardEngine):
         """images: per image u8 [H,W,3] or fp32 [3,H,W] (already resized by the processor rule).  Returns
         (post-LN features T [P, Dv], patch counts)."""
         ops, W, vc = self.ops, self.W, self.cfg.vision_config
-        P_sz, D, H, hd = vc.patch_size, vc.hidden_size, vc.num_attention_heads, vc.head_dim
+        P_sz, D = vc.patch_size, vc.hidden_size
         counts, pos = [], []
         for im in images:
             ih, iw = (im.shape[0], im.shape[1]) if im.dtype == torch.uint8 else (im.shape[1], im.shape[2])
@@ -175,36 +175,17 @@ class Idefics2Engine(LeopardEngine):
         for n in counts:
             cu_list.append(cu_list[-1] + n)
         cu = self._pinned_to_device(torch.tensor(cu_list, dtype=torch.int32))
-        h = self._empty(M, D)
-        qkv = self._empty(M, W.vit_layers[0].qkv_w.shape[0])
+        out = self._empty(M, D)
         if self.lo4 and self.lo4_vit:
-            # precision "lo4" (LeopardEngine._vit_layers_lo4): every layer-linear operand of the NaViT tower travels with the fp4 image of its
-            # rounding residual; the connector (modality projection + 3 perceiver layers) keeps the fast schedule, the Mistral layers take
-            # LeopardEngine._llm_layers_lo4
-            h4, att4, ff4 = self._lo4_act(M, D), self._lo4_act(M, D, heads=(H, hd)), self._lo4_act(M, W.vit_ff)
-            for L, (qkv4, o4, fc14, fc24) in zip(W.vit_layers, self._lo4_weights("vit")):
-                ops.norm_lo4(x, L.ln1_w, L.ln1_b, h4, vc.layer_norm_eps)
-                ops.gemm_lo4(h4, L.qkv_w, qkv4, qkv, bias=L.qkv_b)
-                ops.attention_lo4(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], att4, cu, cu, max(counts), H, H, hd, hd ** -0.5, False)
-                ops.gemm_lo4(att4, L.o_w, o4, x, bias=L.o_b, epilogue=_lib.EPI_RESIDUAL)
-                ops.norm_lo4(x, L.ln2_w, L.ln2_b, h4, vc.layer_norm_eps)
-                ops.gemm_lo4(h4, L.fc1_w, fc14, ff4.hi, bias=L.fc1_b, act=_lib.ACT_GELU_TANH, out4=ff4)
-                ops.gemm_lo4(ff4, L.fc2_w, fc24, x, bias=L.fc2_b, epilogue=_lib.EPI_RESIDUAL)
-            ops.layernorm(x, W.post_ln_w, W.post_ln_b, h, vc.layer_norm_eps)
-            return h, counts
-        att = self._empty(M, D)
-        ff = self._empty(M, W.vit_ff)
-        for L in W.vit_layers:
-            ops.layernorm(x, L.ln1_w, L.ln1_b, h, vc.layer_norm_eps)
-            ops.gemm(h, L.qkv_w, qkv, bias=L.qkv_b)
-            ops.attention(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], att, cu, cu, max(counts), H, H, hd, hd ** -0.5,
-                          False, self.use_tr)
-            ops.gemm(att, L.o_w, x, bias=L.o_b, epilogue=_lib.EPI_RESIDUAL)
-            ops.layernorm(x, L.ln2_w, L.ln2_b, h, vc.layer_norm_eps)
-            ops.gemm(h, L.fc1_w, ff, bias=L.fc1_b, act=_lib.ACT_GELU_TANH)
-            ops.gemm(ff, L.fc2_w, x, bias=L.fc2_b, epilogue=_lib.EPI_RESIDUAL)
-        ops.layernorm(x, W.post_ln_w, W.post_ln_b, h, vc.layer_norm_eps)
-        return h, counts
+            # precision "lo4" (LeopardEngine._vit_layers on Lo4Act operands): every layer-linear operand of the NaViT tower travels with the fp4
+            # image of its rounding residual; the connector (modality projection + 3 perceiver layers) keeps the fast schedule, the Mistral
+            # layers take the lo4 side of LeopardEngine._llm_layers
+            operands, w4s = self._vit_operands_lo4(M), self._lo4_weights("vit")
+        else:
+            operands, w4s = (out, self._empty(M, W.vit_layers[0].qkv_w.shape[0]), self._empty(M, D), self._empty(M, W.vit_ff)), None
+        self._vit_layers(x, cu, max(counts), operands, w4s)
+        ops.layernorm(x, W.post_ln_w, W.post_ln_b, out, vc.layer_norm_eps)
+        return out, counts
 
     # ---- connector: modality projection + perceiver resampler --------------------------------------------------
     def connector(self, feats: torch.Tensor, counts: Sequence[int]) -> torch.Tensor:

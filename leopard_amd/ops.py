@@ -91,6 +91,11 @@ def lo4_packed_act(M: int, K: int, dtype, device) -> Lo4Act:
     return act
 
 
+def rows_from(a, row0: int, sel: Optional[tuple] = None):
+    """The rows row0.. of an operand of either kind (the last layer's row window): ``t[row0:]`` of a tensor, ``rows_from`` of a Lo4Act."""
+    return a.rows_from(row0, sel) if isinstance(a, Lo4Act) else a[row0:]
+
+
 class Lo4Weight:
     """fp4 image of a weight [N, K4 / 2] bytes (row-major, whatever the layout of the 16-bit copy) + one E8M0 scale per row [N]."""
     __slots__ = ("img", "sc")
@@ -592,6 +597,56 @@ class Ops:
                                                   a.hi.stride(0), self._ldw(w_qkv_rope), qkv.stride(0), C.byref(d), _DT[w_qkv_rope.dtype],
                                                   self._stream(qkv)))
         return qkv
+
+    # ---- one layer body for the fast and the lo4 schedule: the OPERAND chooses the entry --------------------------------------------------
+    # A plain tensor takes the 16-bit entry, a Lo4Act the _lo4 entry (with the fp4 image ``w4`` of the weight).  A Lo4Act given as a
+    # destination stands for "its ``hi`` rows, and the image of their rounding residual beside them".
+    def linear(self, a, w, out, w4: Optional[Lo4Weight] = None, bias=None, epilogue=EPI_STORE, act=ACT_NONE, rowsq_in=None, norm_dim=0, norm_eps=0.0,
+               norm_out=None, norm_gamma=None, rowsq_out=None):
+        """out = epilogue(a @ w.T): gemm_lo4 for a Lo4Act ``a``; gemm_ex for a tensor with a folded-norm argument; gemm otherwise.
+        ``out`` (STORE / SWIGLU) or ``norm_out`` (the RESIDUAL producer) may be a Lo4Act."""
+        if isinstance(a, Lo4Act):
+            if w4 is None:
+                raise TypeError("leopard_amd: a Lo4Act operand needs the fp4 image of the weight (w4)")
+            out4 = None
+            if isinstance(norm_out, Lo4Act):
+                out4, norm_out = norm_out, norm_out.hi
+            elif isinstance(out, Lo4Act):
+                out4, out = out, out.hi
+            return self.gemm_lo4(a, w, w4, out, bias, epilogue, act, rowsq_in, norm_dim, norm_eps, norm_out, norm_gamma, rowsq_out, out4)
+        if rowsq_in is not None or norm_out is not None or rowsq_out is not None:
+            return self.gemm_ex(a, w, out, bias, epilogue, act, rowsq_in, norm_dim, norm_eps, norm_out, norm_gamma, rowsq_out)
+        return self.gemm(a, w, out, bias=bias, epilogue=epilogue, act=act)
+
+    def qkv_rope(self, a, w_qkv_rope, qkv, rowsq_in, eps, cos, sin, k_cache, v_cache, cache_pos0, n_q_heads, n_kv_heads, head_dim,
+                 w4: Optional[Lo4Weight] = None):
+        """rmsnorm_rope / rmsnorm_rope_lo4 by the type of ``a``."""
+        if isinstance(a, Lo4Act):
+            return self.rmsnorm_rope_lo4(a, w_qkv_rope, w4, qkv, rowsq_in, eps, cos, sin, k_cache, v_cache, cache_pos0, n_q_heads, n_kv_heads, head_dim)
+        return self.rmsnorm_rope(a, w_qkv_rope, qkv, rowsq_in, eps, cos, sin, k_cache, v_cache, cache_pos0, n_q_heads, n_kv_heads, head_dim)
+
+    def norm(self, x, w, b, out, eps):
+        """LayerNorm (b given) / RMSNorm (b None) of the fp32 rows x into a 16-bit tensor, or into a Lo4Act (norm_lo4)."""
+        if isinstance(out, Lo4Act):
+            return self.norm_lo4(x, w, b, out, eps)
+        return self.rmsnorm(x, w, out, eps) if b is None else self.layernorm(x, w, b, out, eps)
+
+    def add_norm(self, x, delta, w, out, eps):
+        """add_rmsnorm / add_rmsnorm_lo4 by the type of ``out``."""
+        if isinstance(out, Lo4Act):
+            return self.add_rmsnorm_lo4(x, delta, w, out, eps)
+        return self.add_rmsnorm(x, delta, w, out, eps)
+
+    def attend(self, q, k, v, out, cu_q, cu_k, max_seqlen_q, n_heads, n_kv_heads, head_dim, scale, causal, use_tr=True, window=0):
+        """attention / attention_lo4 by the type of ``out`` (``use_tr`` is a knob of the 16-bit entry alone)."""
+        if isinstance(out, Lo4Act):
+            return self.attention_lo4(q, k, v, out, cu_q, cu_k, max_seqlen_q, n_heads, n_kv_heads, head_dim, scale, causal, window=window)
+        return self.attention(q, k, v, out, cu_q, cu_k, max_seqlen_q, n_heads, n_kv_heads, head_dim, scale, causal, use_tr, window=window)
+
+    def attend_prefix(self, q, k, v, k_prefix, v_prefix, prefix_len, out, cu, max_seqlen_q, n_heads, n_kv_heads, head_dim, scale):
+        """attention_prefix / attention_prefix_lo4 by the type of ``out``."""
+        fn = self.attention_prefix_lo4 if isinstance(out, Lo4Act) else self.attention_prefix
+        return fn(q, k, v, k_prefix, v_prefix, prefix_len, out, cu, max_seqlen_q, n_heads, n_kv_heads, head_dim, scale)
 
     def split_rows_hl(self, x_f32, out):
         """out [2 M, K] (16-bit) = rows T(x), then rows T(x - T(x)) of the fp32 x [M, K] (lmi_split_rows_hl; the decode precision mode)."""

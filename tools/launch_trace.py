@@ -2,7 +2,8 @@
 
 Every kernel goes through ``Ops.lib.<lmi_...>``.  This script wraps the emulator build of the library (``make emu``) in a recording proxy
 (entry name + every non-pointer scalar argument; a pointer is recorded as null / non-null only), drives LeopardEngine through its host
-paths on the micro configuration of tests/test_emu_engine.py (LLM width 256, which the lo4 schedule needs) and prints one SHA-256 per scenario.  Two commits whose engine issues the
+paths on the micro configuration of tests/test_emu_engine.py (LLM width 256, which the lo4 schedule needs) — and Idefics2Engine and the
+tensor-parallel loop (rank 0 of 2 over a loop-back communicator) on theirs — and prints one SHA-256 per scenario.  Two commits whose engine issues the
 same launches print the same hashes: the check for a refactor of the host plumbing (``--dump DIR`` writes the traces themselves).
 
     make emu && python tools/launch_trace.py
@@ -21,7 +22,8 @@ import torch         # noqa: E402
 
 from leopard_amd import _lib                                                            # noqa: E402
 from leopard_amd.config import LeopardConfig, RopeScaling, TextConfig, VisionConfig     # noqa: E402
-from leopard_amd.engine import LeopardEngine, SamplingParams                            # noqa: E402
+from leopard_amd.dist import Comm                                                       # noqa: E402
+from leopard_amd.engine import KVCache, LeopardEngine, SamplingParams                   # noqa: E402
 from leopard_amd.ops import Ops                                                         # noqa: E402
 from leopard_amd.weights import EngineWeights, SynthSource                              # noqa: E402
 
@@ -63,6 +65,25 @@ def micro_config(vit_layers=1):
         text_config=TextConfig(hidden_size=256, intermediate_size=128, num_hidden_layers=2, num_attention_heads=2,
                                num_key_value_heads=1, vocab_size=256, rope_scaling=RopeScaling()),
         image_token_index=250)
+
+
+class LoopbackComm(Comm):
+    """Rank 0 of a two-rank group without a second process: every collective hands the rank its own block back, so the tensor-parallel
+    loop issues the launches of a real rank 0 (the values are not those of a two-rank run)."""
+    rank, world, backend = 0, 2, "loopback"
+
+    def all_gather(self, out, inp, stream=None):
+        out.view(self.world, *inp.shape).copy_(inp.unsqueeze(0).expand(self.world, *inp.shape))
+
+    def reduce_scatter(self, out, inp, stream=None):
+        out.copy_(inp[:out.shape[0]])
+
+    def all_reduce(self, t, stream=None):
+        pass
+
+    def broadcast(self, t, root, stream=None):
+        if root != self.rank:
+            t.zero_()
 
 
 def tiles(seed, n):
@@ -145,6 +166,59 @@ def scenarios(ops):
         eng.enable_fp8([(torch.tensor([[3, 250, 250, 8]]), tiles(9, 2))])
         return lambda: eng.prefill(ids3, tiles(3, 3), all_logits=True)
     out["prefill_fp8"] = fp8()
+
+    # the paths a fold of the fast and lo4 layer loops rewrites: the last layer's row window, the continuation arguments, the NaViT tower of
+    # Idefics2Engine and the tensor-parallel loop
+    def last_layer_window(mode):
+        eng = engine(ops)
+        eng.precision, eng.lo4_rows = mode, 16
+        ids = torch.tensor([[int(v) for v in np.random.default_rng(3).integers(0, 240, 300)]])
+        return lambda: eng.prefill(ids, None, cache=KVCache(eng.cfg, 300, torch.float16, "cpu"))
+
+    def continuation(mode):
+        eng = engine(ops)
+        eng.precision = mode
+        sfx = [torch.tensor([[7, 8, 9]]), torch.tensor([[11, 12, 13, 14, 15]])]
+
+        def run():
+            cache = KVCache(eng.cfg, 32, torch.float16, "cpu")
+            eng.prefill(ids3[:, :4], tiles(3, 2), cache=cache)
+            eng.extend(cache, sfx, kv_out=KVCache(eng.cfg, 8, torch.float16, "cpu"))
+            eng.append(cache, torch.tensor([[21, 22, 23]]))
+            eng.generate_shared(ids3[:, :4], tiles(3, 2), sfx, max_new_tokens=3, eos_token_id=())
+        return run
+
+    def idefics2(mode):
+        from leopard_amd.config import Idefics2Config, PerceiverConfig
+        from leopard_amd.idefics2 import Idefics2Engine, Idefics2SynthSource, Idefics2Weights
+        cfg = Idefics2Config(
+            vision_config=VisionConfig(hidden_size=1152, intermediate_size=100, num_hidden_layers=1, num_attention_heads=16,
+                                       image_size=56, patch_size=14),
+            text_config=TextConfig(hidden_size=256, intermediate_size=128, num_hidden_layers=2, num_attention_heads=2,
+                                   num_key_value_heads=1, vocab_size=256, rope_theta=10000.0, rope_scaling=None, sliding_window=6),
+            perceiver_config=PerceiverConfig(n_latents=3, depth=2, n_heads=1, head_dim=96, num_key_value_heads=1),
+            image_token_id=250, longest_edge=56)
+        eng = Idefics2Engine(cfg, Idefics2Weights.build(cfg, Idefics2SynthSource(cfg, ops, "cpu", torch.float16), torch.float16), ops=ops,
+                             device="cpu")
+        eng.precision = mode
+        rng = np.random.default_rng(8)
+        images = [torch.from_numpy(rng.standard_normal(s).astype(np.float32)) for s in ((3, 42, 56), (3, 58, 30))]
+        ids = torch.tensor([[5, 7] + [250] * 3 + [9, 11, 13] + [250] * 3 + [17, 19]])
+        return lambda: eng.prefill(ids, images)
+
+    def tensor_parallel(mode):
+        cfg = micro_config()
+        cfg.text_config = TextConfig(hidden_size=512, intermediate_size=256, num_hidden_layers=2, num_attention_heads=4,
+                                     num_key_value_heads=2, vocab_size=256, rope_scaling=RopeScaling())
+        W = EngineWeights.build(cfg, SynthSource(cfg, ops, "cpu", torch.float16), torch.float16, tp_rank=0, tp_size=2)
+        eng = LeopardEngine(cfg, W, ops=ops, device="cpu", comm=LoopbackComm())
+        eng.precision = mode
+        return lambda: eng.prefill(ids3, tiles(3, 3))
+    for mode in ("fast", "lo4"):
+        out[f"last_layer_window_{mode}"] = last_layer_window(mode)
+        out[f"extend_append_shared_{mode}"] = continuation(mode)
+        out[f"idefics2_prefill_{mode}"] = idefics2(mode)
+        out[f"tp_prefill_{mode}"] = tensor_parallel(mode)
     return out
 
 
