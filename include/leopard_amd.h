@@ -476,6 +476,42 @@ int lmi_attn_decode_pool_hl(const void* q, const void* k, const void* v, void* o
                             int ldq, int ldk, int ldv, int ldo, float scale, int window, void* workspace, int64_t workspace_bytes,
                             int dtype, void* stream);
 
+/* Batched decode behind a SHARED PREFIX (several questions about the same images: the prefix K / V exist once and every step reads them
+ * once for the whole batch).  One query row per sequence, row s of q; sequence s attends to
+ *     [k_prefix / v_prefix rows 0 .. *prefix_len) ; pooled rows k_begin[s] .. k_begin[s] + k_len[s]) of k / v],
+ * every key of both ranges visible, no sliding window.  The prefix is read in place and never written; *prefix_len (device memory, clamped to
+ * max_prefix_len) and k_len may change between replays of a captured graph: the launch geometry depends on max_prefix_len, max_seqlen_k and
+ * the head counts only — not on n_seq either, so a sequence gets the same bits alone and among batch mates.  Three launches into one partials
+ * workspace: the prefix pass (grid n_kv_heads x prefix splits; wave w of a workgroup takes query head 4 kvh + w and row r of its 32-row
+ * MFMA tile is sequence r; non-temporal loads), the pooled split-KV walk of lmi_attn_decode_pool over the own rows, and one merge over all
+ * splits (at most 64).  Limits (LMI_EINVAL otherwise): head_dim 128, n_heads == 4 * n_kv_heads, 1 <= n_seq <= 32, q_rows >= n_seq,
+ * max_prefix_len >= 1, row strides multiples of 8 and at least the heads' width, each range's rows within 4 GiB.
+ * _hl: out has 2 * q_rows rows, as lmi_attn_decode_pool_hl.  workspace: lmi_attn_decode_shared_workspace_bytes(...) bytes, 16-byte aligned. */
+int64_t lmi_attn_decode_shared_workspace_bytes(int q_rows, int n_heads, int head_dim, int max_prefix_len, int max_seqlen_k);
+int lmi_attn_decode_shared(const void* q, const void* k_prefix, const void* v_prefix, const int* prefix_len, int max_prefix_len, const void* k, const void* v,
+                           void* out, const int* k_begin, const int* k_len, int n_seq, int max_seqlen_k, int q_rows, int n_heads, int n_kv_heads,
+                           int head_dim, int ldq, int ldkp, int ldvp, int ldk, int ldv, int ldo, float scale, void* workspace, int64_t workspace_bytes,
+                           int dtype, void* stream);
+int lmi_attn_decode_shared_hl(const void* q, const void* k_prefix, const void* v_prefix, const int* prefix_len, int max_prefix_len, const void* k, const void* v,
+                              void* out, const int* k_begin, const int* k_len, int n_seq, int max_seqlen_k, int q_rows, int n_heads, int n_kv_heads,
+                              int head_dim, int ldq, int ldkp, int ldvp, int ldk, int ldv, int ldo, float scale, void* workspace, int64_t workspace_bytes,
+                              int dtype, void* stream);
+
+/* The KV append at a biased row, for slots that hold only a sequence's own rows behind such a prefix: as lmi_rope_qkv_skinny / _hl and
+ * lmi_rope_qk_rows, but row m appends to row m * cache_stride + pos_rows_dev[m] - *row_bias_dev of the pooled caches while it still rotates at
+ * pos_rows_dev[m].  row_bias_dev is a device int (one captured step serves prefixes of any length); null = the unbiased call, bit for bit. */
+int lmi_rope_qkv_skinny_biased(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,
+                               int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all, const float* sin_all,
+                               void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, const int* row_bias_dev, int dtype,
+                               void* stream);
+int lmi_rope_qkv_skinny_hl_biased(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,
+                                  int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all, const float* sin_all,
+                                  void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, const int* row_bias_dev,
+                                  int dtype, void* stream);
+int lmi_rope_qk_rows_biased(void* qkv, int S, int ld, int n_q_heads, int n_kv_heads, int head_dim, const float* cos_all, const float* sin_all,
+                            void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, const int* row_bias_dev, int dtype,
+                            void* stream);
+
 /* Same with the RMSNorm of the decode step folded in: x is the fp32 residual row [K], norm_weight fp32 [K], and the row
  * fed to the product is T(norm_weight * (x * rsqrt(mean(x^2) + eps))) — the arithmetic of lmi_rmsnorm, without its launch.
  * K = 4096 (the hidden size of Llama-3.1-8B / Mistral-7B). */

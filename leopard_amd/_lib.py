@@ -83,6 +83,12 @@ SIGNATURES = {
     "lmi_split_rows_hl": [_P, _P, _I, _I, _I, _I, _I, _P],
     "lmi_attn_decode_fwd_hl": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P, C.c_int64, _I, _P],
     "lmi_attn_decode_pool_hl": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P, C.c_int64, _I, _P],
+    "lmi_attn_decode_shared_workspace_bytes": [_I, _I, _I, _I, _I],      # restype int64 (bind)
+    "lmi_attn_decode_shared": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, C.c_int64, _I, _P],
+    "lmi_attn_decode_shared_hl": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, C.c_int64, _I, _P],
+    "lmi_rope_qkv_skinny_biased": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _F, _P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P],
+    "lmi_rope_qkv_skinny_hl_biased": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _F, _P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P],
+    "lmi_rope_qk_rows_biased": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P],
     "lmi_debug_copy": [_P, _P, C.c_int64, _I, _P],
     "lmi_gemm_skinny": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "lmi_decode_advance": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P],
@@ -110,6 +116,7 @@ def bind(path: str) -> C.CDLL:
         fn.restype = C.c_int
     lib.lmi_attn_decode_workspace_bytes.argtypes = [_I, _I, _I, _I]
     lib.lmi_attn_decode_workspace_bytes.restype = C.c_int64
+    lib.lmi_attn_decode_shared_workspace_bytes.restype = C.c_int64
     lib.lmi_llm_prefill_workspace_bytes.argtypes = [C.c_int64, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int64)]
     lib.lmi_llm_prefill_workspace_bytes.restype = C.c_int64
     lib.lmi_vit_workspace_bytes.argtypes = [C.c_int64, _I, _I, _I, _I, C.POINTER(C.c_int64)]

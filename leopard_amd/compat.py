@@ -203,16 +203,19 @@ class LeopardForConditionalGeneration:
 
     @torch.no_grad()
     def generate_shared(self, prefix_ids, pixel_values, suffix_ids_list: Sequence[torch.Tensor], eos_token_id=None, max_new_tokens: int = 128,
-                        do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None, **unused) -> List[torch.Tensor]:
+                        do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None, decode: str = "copy",
+                        **unused) -> List[torch.Tensor]:
         """Many questions about one set of images: ``prefix_ids`` [1, S_p] (the chat head and every image group, with ``pixel_values``) is
         prefilled ONCE — the vision tower runs once — and the text-only ``suffix_ids_list`` ([1, s_j] each: question, instruction, tail)
         continue from its cache together (LeopardEngine.generate_shared).  Returns [LongTensor [1, S_p + s_j + T]], each what ``generate``
-        returns for the concatenated prompt.  Decoding kwargs as ``generate_batch``; request i draws with its own seed.  Memory: every decode
-        slot holds its own copy of the prefix rows, B x (P + s + T) rows per layer."""
+        returns for the concatenated prompt.  Decoding kwargs as ``generate_batch``; request i draws with its own seed.  Memory: with
+        ``decode`` = "copy" (the default) every decode slot holds its own copy of the prefix rows, B x (P + s + T) rows per layer; with
+        ``decode`` = "shared" the prefix is stored once and read once per step for the whole batch — about P + B x (s + T) rows per layer
+        (head_dim 128 and 4 query heads per KV head; NotImplementedError otherwise)."""
         sp = self._sampling("generate_shared", unused, do_sample, temperature, top_k, top_p, seed)
         eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
         return self.engine.generate_shared(prefix_ids.to(self.device), self._as_tiles(pixel_values), [s.to(self.device) for s in suffix_ids_list],
-                                           max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp)
+                                           max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp, decode=decode)
 
     @torch.no_grad()
     def generate_stream(self, requests: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8, eos_token_id=None,

@@ -66,7 +66,13 @@ struct AttnArgs {
     const void* k_prefix;     // head kvh at k_prefix + row*ldkp + kvh*D; null = no prefix
     const void* v_prefix;
     int ldkp, ldvp;
-    int prefix_len;           // P >= 1 (host integer)
+    int prefix_len;           // P >= 1 (host integer); the SHARED instantiation: the capacity that bounds the device-resident length
+    // Decode with a shared prefix (lmi_attn_decode_shared): two walks write their partials into one workspace and one merge reads them all.
+    //   * prefix pass (the SHARED instantiation): ONE key range — k / v are the prefix rows [0, min(k_len[0], prefix_len)), the length in device
+    //     memory — and query row r of q is the current token of sequence r (shared_rows <= 32 of them: one GQA-packed row block);
+    //   * own pass (cu_q == null): one query row per sequence, row s of q, against the pooled rows cu_k[s] .. cu_k[s] + k_len[s]).
+    int split_base = 0;       // the partials of this launch are splits split_base .. split_base + n_splits) of the workspace
+    int shared_rows = 0;
 };
 
 constexpr int ATT_BQ = 128, ATT_BKV = 64, ATT_THREADS = 256;
@@ -329,9 +335,15 @@ LMI_DEV int att_vchunk72(int r4, int pos) {                    // inverse: which
 // in mid-stream); tiles t >= PT are the sequence's own rows, restarting at own row 0, causal as ever.  The tiles are walked in key order, so
 // with P a multiple of 64 the partition — and every bit of the result — is that of a launch over a contiguous copy [prefix ; own].  Every
 // tile, of either range, is the same 2 * PPW pieces per wave into the same ring: the vmcnt(0) + barrier hand-over is untouched.
-template <typename T, int D, bool CAUSAL, bool STREAM = false, bool PREFIX = false>      // STREAM: non-temporal K / V loads (decode: each tile is read once)
+//
+// SHARED (the prefix pass of lmi_attn_decode_shared): the 32 rows of a wave's tile are the current tokens of up to 32 SEQUENCES that all see
+// the same keys — the prefix rows, every one of them visible (not causal), walked once for the whole batch.  A row must get the bits it gets
+// when its sequence is decoded alone, so the deferred rescale below moves the reference of a row only when that row's own maximum crossed
+// the threshold (the wave-uniform test still gates the branch).
+template <typename T, int D, bool CAUSAL, bool STREAM = false, bool PREFIX = false, bool SHARED = false>      // STREAM: non-temporal K / V loads (decode: each tile is read once)
 __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p) {
     static_assert(!PREFIX || (CAUSAL && D == 128 && !STREAM), "the prefix range: causal self-attention at head_dim 128");
+    static_assert(!SHARED || (!CAUSAL && D == 128 && !PREFIX), "the shared prefix pass: every key visible, head_dim 128, GQA-packed, split-KV");
     constexpr int NW = ATT_THREADS / 64, BQ = ATT_BQ, PPW = AttnDmaGeom<D>::PPW;
     typedef AttnDmaGeom<D> G;
     constexpr int NKS = G::NKS, NDB = G::NDB;
@@ -356,8 +368,10 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p
     const int qb = p.n_qblocks - 1 - rest % p.n_qblocks, seq = rest / p.n_qblocks;
     const int kvh = h_idx % p.n_kv_heads;
     const int head = pack ? kvh * NW + wave : kvh * (p.n_heads / p.n_kv_heads) + h_idx / p.n_kv_heads;
-    const int q_beg = p.cu_q[seq], len_q = p.cu_q[seq + 1] - q_beg;
-    const int k_beg = p.cu_k[seq], len_k = p.k_len ? p.k_len[seq] : p.cu_k[seq + 1] - k_beg;
+    // cu_q == null: one query row per sequence (row seq); SHARED: the one key range of the launch and its shared_rows query rows
+    const int q_beg = SHARED ? 0 : (p.cu_q ? p.cu_q[seq] : seq), len_q = SHARED ? p.shared_rows : (p.cu_q ? p.cu_q[seq + 1] - q_beg : 1);
+    const int k_beg = SHARED ? 0 : p.cu_k[seq];
+    const int len_k = SHARED ? imax(0, imin(p.k_len[0], p.prefix_len)) : (p.k_len ? p.k_len[seq] : p.cu_k[seq + 1] - k_beg);
     const int bq = pack ? 32 : BQ;                                 // query rows per workgroup
     const int q0 = qb * bq;
     if (q0 >= len_q) return;
@@ -562,13 +576,15 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p
         // multiplies per tile disappear from all but the first few tiles of a row block.
         const float m_cand = fmaxf(m_run, mx);
         if (wave_any((m_cand - m_run) * c2 > ATT_DEFER_LOG2)) {     // -inf - -inf = NaN compares false: nothing seen yet
-            const float alpha = fast_exp2((m_run - ((m_cand == -INFINITY) ? 0.f : m_cand)) * c2);
+            // SHARED: the rows are different sequences — a row that did not cross the threshold itself keeps its reference (alpha = 1)
+            const bool mine = !SHARED || (m_cand - m_run) * c2 > ATT_DEFER_LOG2;
+            const float alpha = mine ? fast_exp2((m_run - ((m_cand == -INFINITY) ? 0.f : m_cand)) * c2) : 1.0f;
             l_run *= alpha;
 #pragma unroll
             for (int i = 0; i < NDB; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) o_acc[i][r] *= alpha;
-            m_run = m_cand;
+            m_run = mine ? m_cand : m_run;
         }
         const float mc = ((m_run == -INFINITY) ? 0.f : m_run) * c2;
         LMI_PROF_TOUCH(o_acc[0][0]);
@@ -619,7 +635,7 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p
     const float l_tot = xhalf_sum(l_run);
     if (p.n_splits > 1) {                                          // unnormalised partial for attn_combine_kernel
         if (my_q < len_q) {
-            const long base = ((long)split * p.part_rows + (q_beg + my_q)) * p.n_heads + head;
+            const long base = ((long)(p.split_base + split) * p.part_rows + (q_beg + my_q)) * p.n_heads + head;
             float* po = p.part_o + base * D;
 #pragma unroll
             for (int db = 0; db < NDB; ++db)
@@ -733,7 +749,7 @@ __global__ void __launch_bounds__(256) attn_combine_kernel(const float* part_o, 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int item = (int)blockIdx.x;
     const int row = item / n_heads, head = item - row * n_heads;
-    if (row >= cu_q[n_seq]) return;                                // whole workgroup
+    if (row >= (cu_q ? cu_q[n_seq] : n_seq)) return;               // whole workgroup (cu_q == null: one query row per sequence)
     const float c2 = scale * 1.4426950408889634f;
     const long stride = (long)part_rows * n_heads;                 // (row, head) items per split
     const long base0 = (long)row * n_heads + head;

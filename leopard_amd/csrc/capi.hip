@@ -560,6 +560,51 @@ int attn_decode_impl(AttnArgs a, int n_seq, int max_q, int q_rows, void* out, in
     return check_launch("lmi_attn_decode_fwd");
 }
 
+// ---- decode attention behind a shared prefix: prefix pass + own pass + one merge -----------------------------------------------------
+// Split geometry, a function of the launch shape only (never of device data: the launch sits in a captured graph while *prefix_len and
+// k_len change; never of n_seq: a sequence alone and the same sequence among batch mates split alike and agree bit for bit).
+//   own range: 64-key tiles per split doubled until at most 8 splits (the slots hold a question and the new tokens: a few tiles);
+//   prefix:    n_kv_heads workgroups per split serve the WHOLE batch, so the splits alone have to fill the device — about 256 workgroups
+//              (where decode_splits stops too), within the 64 - 8 lanes the merge kernel has left.
+struct SharedSplits { int pre_n, pre_tiles, own_n, own_tiles; };
+static SharedSplits decode_shared_splits(int n_kv_heads, int max_prefix_len, int max_seqlen_k) {
+    SharedSplits g;
+    const int to = (max_seqlen_k + ATT_BKV - 1) / ATT_BKV;
+    g.own_tiles = 1;
+    while ((to + g.own_tiles - 1) / g.own_tiles > 8) g.own_tiles *= 2;
+    g.own_n = (to + g.own_tiles - 1) / g.own_tiles;
+    if (g.own_n < 2) g.own_n = 2;                                  // as decode_splits: a single chunk also goes through the partials
+    const int tp = (max_prefix_len + ATT_BKV - 1) / ATT_BKV;
+    int want = (256 + n_kv_heads - 1) / n_kv_heads;
+    if (want > 64 - 8) want = 64 - 8;
+    g.pre_tiles = (tp + want - 1) / want;
+    if (g.pre_tiles < 1) g.pre_tiles = 1;
+    g.pre_n = (tp + g.pre_tiles - 1) / g.pre_tiles;
+    if (g.pre_n < 2) g.pre_n = 2;
+    return g;
+}
+
+template <typename T>
+int attn_decode_shared_impl(AttnArgs pre, AttnArgs own, int n_seq, int q_rows, void* out, int ldo, void* stream, int lo_rows) {
+    static std::atomic<uint64_t> attr_done{0};
+    static std::atomic<uint64_t> attr_done_s{0};
+    static std::atomic<uint64_t> attr_done_p{0};
+    allow_big_lds(attn_fwd_dma_kernel<T, 128, true>, 160 * 1024, attr_done);
+    allow_big_lds(attn_fwd_dma_kernel<T, 128, true, true>, 160 * 1024, attr_done_s);
+    allow_big_lds(attn_fwd_dma_kernel<T, 128, false, true, false, true>, 160 * 1024, attr_done_p);
+    // prefix pass: one GQA-packed row block (row r = sequence r) per (kv head, split); every tile is read once by the whole batch: non-temporal
+    LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, false, true, false, true>), dim3(pre.n_kv_heads * pre.n_splits), dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, pre);
+    // own pass: the pooled split-KV walk of lmi_attn_decode_pool, one query row per sequence
+    const dim3 grid(own.n_kv_heads * n_seq * own.n_splits);
+    if (g_attn_stream_kv.load()) LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, own);
+    else LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, own);
+    const long items = (long)n_seq * own.n_heads;
+    LMI_LAUNCH((attn_combine_kernel<T, 128>), dim3((unsigned)items), dim3(256), 0, stream, (const float*)own.part_o, (const float*)own.part_ml, (T*)out,
+               (const int*)nullptr, n_seq, own.n_heads, pre.n_splits + own.n_splits, own.part_rows, ldo, own.scale, lo_rows);
+    (void)q_rows;
+    return check_launch("lmi_attn_decode_shared");
+}
+
 std::atomic<int> g_skinny_coalesce{1};       // nn.Linear-layout weights of the M <= 16 kernel: 1 = coalescing lane order + ds_bpermute (LAYOUT 2), 0 = MFMA lane order
 template <typename T, int LAYOUT>
 int skinny_impl(const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, void* stream,
@@ -600,8 +645,8 @@ int skinny_norm_args(const char* who, SkinnyNorm& nm, int M, int N, int epilogue
 
 template <typename T>
 int rope_rows_impl(void* qkv, int S, int ld, int nq, int nkv, int D, const float* c, const float* s, void* kc, void* vc, int ldc,
-                          long cache_stride, const int* pos, int grid, void* stream) {
-    LMI_LAUNCH((rope_rows_kernel<T>), dim3(grid), dim3(256), 0, stream, (T*)qkv, S, ld, nq, nkv, D, c, s, (T*)kc, (T*)vc, ldc, cache_stride, pos);
+                          long cache_stride, const int* pos, const int* row_bias, int grid, void* stream) {
+    LMI_LAUNCH((rope_rows_kernel<T>), dim3(grid), dim3(256), 0, stream, (T*)qkv, S, ld, nq, nkv, D, c, s, (T*)kc, (T*)vc, ldc, cache_stride, pos, row_bias);
     return check_launch("lmi_rope_qk_rows");
 }
 
@@ -1427,6 +1472,69 @@ int lmi_attn_decode_pool(const void* q, const void* k, const void* v, void* out,
                              n_heads, n_kv_heads, head_dim, ldq, ldk, ldv, ldo, scale, window, workspace, workspace_bytes, dtype, stream);
 }
 
+int64_t lmi_attn_decode_shared_workspace_bytes(int q_rows, int n_heads, int head_dim, int max_prefix_len, int max_seqlen_k) {
+    if (q_rows < 0 || n_heads <= 0 || (n_heads & 3) || head_dim <= 0 || max_prefix_len < 1 || max_seqlen_k < 0) return -1;
+    const SharedSplits g = decode_shared_splits(n_heads / 4, max_prefix_len, max_seqlen_k);
+    return (int64_t)(g.pre_n + g.own_n) * q_rows * n_heads * (head_dim + 2) * 4;
+}
+
+static int attn_decode_shared_entry(const char* who, const void* q, const void* k_prefix, const void* v_prefix, const int* prefix_len, int max_prefix_len,
+                                    const void* k, const void* v, void* out, const int* k_begin, const int* k_len, int n_seq, int max_seqlen_k, int q_rows,
+                                    int n_heads, int n_kv_heads, int head_dim, int ldq, int ldkp, int ldvp, int ldk, int ldv, int ldo, float scale,
+                                    void* workspace, int64_t workspace_bytes, int dtype, void* stream, int hl) {
+    if (!q || !k_prefix || !v_prefix || !prefix_len || !k || !v || !out || !k_begin || !k_len || !workspace) return fail(LMI_EINVAL, "%s: null pointer", who);
+    if (head_dim != 128) return fail(LMI_EINVAL, "%s: head_dim %d (only 128)", who, head_dim);
+    if (n_heads <= 0 || n_kv_heads <= 0 || n_heads != 4 * n_kv_heads)
+        return fail(LMI_EINVAL, "%s: needs n_heads == 4 * n_kv_heads (a workgroup's 4 waves take the query heads of one kv head), got %d / %d", who, n_heads, n_kv_heads);
+    if (n_seq < 1 || n_seq > 32) return fail(LMI_EINVAL, "%s: n_seq %d (1 .. 32: one row of a wave's 32-row tile per sequence)", who, n_seq);
+    if (max_prefix_len < 1 || max_seqlen_k < 0 || q_rows < n_seq) return fail(LMI_EINVAL, "%s: bad sizes (max_prefix_len >= 1, max_seqlen_k >= 0, q_rows >= n_seq)", who);
+    if ((ldq & 7) || (ldkp & 7) || (ldvp & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) || ldq < n_heads * head_dim || ldo < n_heads * head_dim ||
+        ldkp < n_kv_heads * head_dim || ldvp < n_kv_heads * head_dim || ldk < n_kv_heads * head_dim || ldv < n_kv_heads * head_dim)
+        return fail(LMI_EINVAL, "%s: row strides must be multiples of 8 and at least the heads' width", who);
+    if (!aligned16(q) || !aligned16(k_prefix) || !aligned16(v_prefix) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(workspace))
+        return fail(LMI_EINVAL, "%s: alignment", who);
+    if (((long)max_prefix_len * ldkp + head_dim) * 2 >= (1L << 32) || ((long)max_prefix_len * ldvp + head_dim) * 2 >= (1L << 32))
+        return fail(LMI_EINVAL, "%s: the prefix K / V rows span >= 4 GiB (max_prefix_len %d, ldkp %d, ldvp %d)", who, max_prefix_len, ldkp, ldvp);
+    if (((long)max_seqlen_k * ldk + head_dim) * 2 >= (1L << 32) || ((long)max_seqlen_k * ldv + head_dim) * 2 >= (1L << 32))
+        return fail(LMI_EINVAL, "%s: one sequence's K / V rows span >= 4 GiB (max_seqlen_k %d, ldk %d, ldv %d)", who, max_seqlen_k, ldk, ldv);
+    const int64_t need = lmi_attn_decode_shared_workspace_bytes(q_rows, n_heads, head_dim, max_prefix_len, max_seqlen_k);
+    if (workspace_bytes < need) return fail(LMI_EINVAL, "%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+    const SharedSplits g = decode_shared_splits(n_kv_heads, max_prefix_len, max_seqlen_k);
+    AttnArgs a;
+    a.q = q; a.out = out; a.cu_q = nullptr; a.cu_k = nullptr;
+    a.out_fp8 = nullptr; a.ldo8 = 0; a.out_fp8_scale = 0.f; a.out_f32 = nullptr; a.ldo32 = 0;
+    a.out4 = nullptr; a.out4_scale = nullptr; a.ld_out4 = a.ld_out4s = 0; a.row_sel = nullptr;
+    a.ldq = ldq; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale; a.window = 0;
+    a.k_prefix = nullptr; a.v_prefix = nullptr; a.ldkp = a.ldvp = 0; a.prefix_len = 0;
+    a.check_k_extent = 0; a.gqa_pack = 1; a.n_qblocks = 1;
+    a.part_rows = q_rows;
+    a.part_o = (float*)workspace;
+    a.part_ml = a.part_o + (size_t)(g.pre_n + g.own_n) * q_rows * n_heads * head_dim;
+    AttnArgs pre = a, own = a;
+    pre.k = k_prefix; pre.v = v_prefix; pre.ldk = ldkp; pre.ldv = ldvp; pre.k_len = prefix_len; pre.prefix_len = max_prefix_len; pre.shared_rows = n_seq;
+    pre.n_splits = g.pre_n; pre.split_tiles = g.pre_tiles; pre.split_base = 0;
+    own.k = k; own.v = v; own.ldk = ldk; own.ldv = ldv; own.cu_k = k_begin; own.k_len = k_len;
+    own.n_splits = g.own_n; own.split_tiles = g.own_tiles; own.split_base = g.pre_n;
+    LMI_DISPATCH_T(dtype, (attn_decode_shared_impl<f16_t>(pre, own, n_seq, q_rows, out, ldo, stream, hl ? q_rows : 0)),
+                   (attn_decode_shared_impl<bf16_t>(pre, own, n_seq, q_rows, out, ldo, stream, hl ? q_rows : 0)));
+}
+
+int lmi_attn_decode_shared(const void* q, const void* k_prefix, const void* v_prefix, const int* prefix_len, int max_prefix_len, const void* k, const void* v,
+                           void* out, const int* k_begin, const int* k_len, int n_seq, int max_seqlen_k, int q_rows, int n_heads, int n_kv_heads,
+                           int head_dim, int ldq, int ldkp, int ldvp, int ldk, int ldv, int ldo, float scale, void* workspace, int64_t workspace_bytes,
+                           int dtype, void* stream) {
+    return attn_decode_shared_entry("lmi_attn_decode_shared", q, k_prefix, v_prefix, prefix_len, max_prefix_len, k, v, out, k_begin, k_len, n_seq, max_seqlen_k,
+                                    q_rows, n_heads, n_kv_heads, head_dim, ldq, ldkp, ldvp, ldk, ldv, ldo, scale, workspace, workspace_bytes, dtype, stream, 0);
+}
+
+int lmi_attn_decode_shared_hl(const void* q, const void* k_prefix, const void* v_prefix, const int* prefix_len, int max_prefix_len, const void* k, const void* v,
+                              void* out, const int* k_begin, const int* k_len, int n_seq, int max_seqlen_k, int q_rows, int n_heads, int n_kv_heads,
+                              int head_dim, int ldq, int ldkp, int ldvp, int ldk, int ldv, int ldo, float scale, void* workspace, int64_t workspace_bytes,
+                              int dtype, void* stream) {
+    return attn_decode_shared_entry("lmi_attn_decode_shared_hl", q, k_prefix, v_prefix, prefix_len, max_prefix_len, k, v, out, k_begin, k_len, n_seq, max_seqlen_k,
+                                    q_rows, n_heads, n_kv_heads, head_dim, ldq, ldkp, ldvp, ldk, ldv, ldo, scale, workspace, workspace_bytes, dtype, stream, 1);
+}
+
 static int gemm_skinny_entry(const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, int packed,
                              const float* rowsq_in, int rowsq_parts, int norm_dim, float norm_eps, void* norm_out, int ld_norm, const float* norm_gamma,
                              float* rowsq_out, int dtype, void* stream, int hl) {
@@ -1494,7 +1602,8 @@ int lmi_gemm_skinny(const void* W, const void* X, void* out, int M, int N, int K
 
 static int rope_qkv_skinny_entry(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,
                                  int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all, const float* sin_all,
-                                 void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, int dtype, void* stream, int hl) {
+                                 void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, int dtype, void* stream, int hl,
+                                 const int* row_bias_dev = nullptr) {
     if (hl && 2 * M > 16) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny_hl: the hi + lo row pairs need 2 M <= 16 (M = %d)", M);
     if (!Wqkv_rope || !X || !qkv || !cos_all || !sin_all || !k_cache || !v_cache || !pos_rows_dev) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny: null pointer");
     if (head_dim != 128) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny: head_dim %d (only 128)", head_dim);
@@ -1508,7 +1617,7 @@ static int rope_qkv_skinny_entry(const void* Wqkv_rope, const void* X, void* qkv
     if (M == 0) return LMI_OK;
     RopeEpi rp;
     rp.cos_all = cos_all; rp.sin_all = sin_all; rp.pos = pos_rows_dev; rp.k_cache = k_cache; rp.v_cache = v_cache; rp.ld_cache = ld_cache;
-    rp.cache_stride = (long)cache_stride; rp.rope_q = n_q_heads * head_dim; rp.rope_k = n_kv_heads * head_dim;
+    rp.cache_stride = (long)cache_stride; rp.rope_q = n_q_heads * head_dim; rp.rope_k = n_kv_heads * head_dim; rp.row_bias = row_bias_dev;
     if (packed)
         LMI_DISPATCH_T(dtype, (skinny_impl<f16_t, 1>(Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)),
                        (skinny_impl<bf16_t, 1>(Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)));
@@ -1533,16 +1642,39 @@ int lmi_rope_qkv_skinny_hl(const void* Wqkv_rope, const void* X, void* qkv, int 
                                  sin_all, k_cache, v_cache, ld_cache, cache_stride, pos_rows_dev, dtype, stream, 1);
 }
 
-int lmi_rope_qk_rows(void* qkv, int S, int ld, int n_q_heads, int n_kv_heads, int head_dim, const float* cos_all, const float* sin_all,
-                     void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, int dtype, void* stream) {
+int lmi_rope_qkv_skinny_biased(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,
+                               int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all, const float* sin_all,
+                               void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, const int* row_bias_dev, int dtype,
+                               void* stream) {
+    return rope_qkv_skinny_entry(Wqkv_rope, X, qkv, M, n_q_heads, n_kv_heads, head_dim, K, ldw, ldx, ldo, packed, rowsq_in, rowsq_parts, norm_eps, cos_all,
+                                 sin_all, k_cache, v_cache, ld_cache, cache_stride, pos_rows_dev, dtype, stream, 0, row_bias_dev);
+}
+
+int lmi_rope_qkv_skinny_hl_biased(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,
+                                  int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all, const float* sin_all,
+                                  void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, const int* row_bias_dev,
+                                  int dtype, void* stream) {
+    return rope_qkv_skinny_entry(Wqkv_rope, X, qkv, M, n_q_heads, n_kv_heads, head_dim, K, ldw, ldx, ldo, packed, rowsq_in, rowsq_parts, norm_eps, cos_all,
+                                 sin_all, k_cache, v_cache, ld_cache, cache_stride, pos_rows_dev, dtype, stream, 1, row_bias_dev);
+}
+
+int lmi_rope_qk_rows_biased(void* qkv, int S, int ld, int n_q_heads, int n_kv_heads, int head_dim, const float* cos_all, const float* sin_all,
+                            void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, const int* row_bias_dev, int dtype,
+                            void* stream) {
     if (!qkv || !cos_all || !sin_all || !k_cache || !v_cache || !pos_rows_dev || S < 0 || (head_dim & 15) || (ld & 7) || (ld_cache & 7) ||
         cache_stride <= 0 || !aligned16(qkv) || !aligned16(k_cache) || !aligned16(v_cache))
         return fail(LMI_EINVAL, "lmi_rope_qk_rows: bad argument");
     if (S == 0) return LMI_OK;
     const long work = (long)S * ((n_q_heads + n_kv_heads) * (head_dim / 16) + n_kv_heads * head_dim / 8);
     const int grid = grid_for(work, 256);
-    LMI_DISPATCH_T(dtype, (rope_rows_impl<f16_t>(qkv, S, ld, n_q_heads, n_kv_heads, head_dim, cos_all, sin_all, k_cache, v_cache, ld_cache, (long)cache_stride, pos_rows_dev, grid, stream)),
-                   (rope_rows_impl<bf16_t>(qkv, S, ld, n_q_heads, n_kv_heads, head_dim, cos_all, sin_all, k_cache, v_cache, ld_cache, (long)cache_stride, pos_rows_dev, grid, stream)));
+    LMI_DISPATCH_T(dtype, (rope_rows_impl<f16_t>(qkv, S, ld, n_q_heads, n_kv_heads, head_dim, cos_all, sin_all, k_cache, v_cache, ld_cache, (long)cache_stride, pos_rows_dev, row_bias_dev, grid, stream)),
+                   (rope_rows_impl<bf16_t>(qkv, S, ld, n_q_heads, n_kv_heads, head_dim, cos_all, sin_all, k_cache, v_cache, ld_cache, (long)cache_stride, pos_rows_dev, row_bias_dev, grid, stream)));
+}
+
+int lmi_rope_qk_rows(void* qkv, int S, int ld, int n_q_heads, int n_kv_heads, int head_dim, const float* cos_all, const float* sin_all,
+                     void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, int dtype, void* stream) {
+    return lmi_rope_qk_rows_biased(qkv, S, ld, n_q_heads, n_kv_heads, head_dim, cos_all, sin_all, k_cache, v_cache, ld_cache, cache_stride, pos_rows_dev,
+                                   nullptr, dtype, stream);
 }
 
 int lmi_rope_qk(void* qkv, int S, int ld, int n_q_heads, int n_kv_heads, int head_dim, const float* cos_table,

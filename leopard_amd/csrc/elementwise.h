@@ -575,6 +575,8 @@ struct RopeEpi {
     int ld_cache;
     long cache_stride;
     int rope_q, rope_k;       // columns [0, rope_q) are q heads, [rope_q, rope_q + rope_k) k heads, the rest v
+    const int* row_bias = nullptr;   // skinny_gemm_kernel only, optional device int: row m appends at m * cache_stride + pos[m] - *row_bias (it still
+                                     // rotates at pos[m]) — slots that hold only a sequence's OWN rows behind a shared prefix of *row_bias positions
 };
 
 

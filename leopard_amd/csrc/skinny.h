@@ -32,7 +32,8 @@ enum { SK_STORE_T = 0, SK_RESID_F32 = 1, SK_SWIGLU_T = 2, SK_STORE_F32 = 3, SK_Q
 // weights.rope_permute_rows order (q / k heads stored as d = [0..31, 64..95, 32..63, 96..127]), so that the two 16-row blocks a workgroup
 // owns — rows r and r + 32 of a 64-row group, exactly the SwiGLU pairing — hold first-half elements and their rotate-half partners.
 // Row m of the batch rotates at its own position pos[m] (device memory) and appends K / V to row m * cache_stride + pos[m] of the pooled
-// caches; v rows (natural order) are two independent blocks.
+// caches; v rows (natural order) are two independent blocks.  RopeEpi::row_bias (optional, device memory) is subtracted from the append row only:
+// the slots of a shared-prefix decode batch hold a sequence's own rows, whose positions start at the prefix length.
 
 // The RMSNorms of the batched decode step folded into its projections, as lmi_gemm_ex does for the prefill (gemm.h GemmRowScale):
 //   producer (SK_RESID_F32, norm_out != null): after x += acc it also writes norm_out[m, n] = T(x[m, n] * gamma[n]) — the next norm's
@@ -166,7 +167,7 @@ __global__ void __launch_bounds__(512) skinny_gemm_kernel(const T* W, const T* X
                 const int c1 = row0 + n, c2 = c1 + 32;              // the two columns (in W's row order) this thread finishes
                 T* orow = (T*)out + (long)m * ldo;
                 const int p = rp.pos[m];
-                const long crow = (long)m * rp.cache_stride + p;
+                const long crow = (long)m * rp.cache_stride + p - (rp.row_bias ? *rp.row_bias : 0);
                 if (c1 >= rp.rope_q + rp.rope_k) {                   // v: natural order, two plain values
                     const int vc = rp.rope_q + rp.rope_k;
                     orow[c1] = (T)v[0];
@@ -232,7 +233,7 @@ __global__ void __launch_bounds__(512) skinny_gemm_kernel(const T* W, const T* X
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void rope_rows_kernel(T* qkv, int S, int ld, int n_q, int n_kv, int D, const float* cosT, const float* sinT,
-                                 T* k_cache, T* v_cache, int ld_cache, long cache_stride, const int* pos) {
+                                 T* k_cache, T* v_cache, int ld_cache, long cache_stride, const int* pos, const int* row_bias) {
     typedef typename vec_of<T>::x8 T8;
     const int half = D >> 1, cpr = half >> 3;
     const int rot_heads = n_q + n_kv;
@@ -243,7 +244,7 @@ __global__ void rope_rows_kernel(T* qkv, int S, int ld, int n_q, int n_kv, int D
         int w = (int)(idx - (long)s * per_tok);
         const int p = pos[s];
         T* row = qkv + (long)s * ld;
-        const long crow = (long)s * cache_stride + p;
+        const long crow = (long)s * cache_stride + p - (row_bias ? *row_bias : 0);     // row_bias: see RopeEpi::row_bias
         if (w < rot_heads * cpr) {
             const int h = w / cpr, c = w - h * cpr;
             T* p1 = row + h * D + c * 8;

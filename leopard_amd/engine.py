@@ -204,6 +204,12 @@ class DecodeState:
     k: Optional[List[torch.Tensor]] = None
     v: Optional[List[torch.Tensor]] = None
     k_len: Optional[torch.Tensor] = None
+    # the shared-prefix pooled step only (_shared_state): ONE copy of the prefix K / V per layer, owned by the state (the captured step holds
+    # no pointer into caller memory); the slots above then hold a sequence's OWN rows (capacity = own rows) and positions start at prefix_len
+    kp: Optional[List[torch.Tensor]] = None      # [prefix_capacity, KV hd] per layer
+    vp: Optional[List[torch.Tensor]] = None
+    prefix_capacity: int = 0
+    prefix_len: Optional[torch.Tensor] = None    # int32 [1], device: the attention's prefix length AND the append's row bias
     live: Optional[torch.Tensor] = None
     budget: Optional[torch.Tensor] = None
     eos: Optional[torch.Tensor] = None
@@ -1563,13 +1569,16 @@ class LeopardEngine:
     # HIP graph over static buffers; the token id and the position live in device memory (lmi_rope_qk_at, device
     # cu_seqlens), the graph itself takes the argmax and advances the position, and the host only reads the new token.
     # ------------------------------------------------------------------------------------------------
-    def _decode_buffers(self, B: int, capacity: int) -> DecodeState:
-        """What the batch-1 and the pooled decode state allocate alike: a function of (B, capacity) under the engine's current mode."""
+    def _decode_buffers(self, B: int, capacity: int, prefix_capacity: int = 0) -> DecodeState:
+        """What the batch-1 and the pooled decode state allocate alike: a function of (B, capacity) under the engine's current mode
+        (``prefix_capacity`` > 0: the shared-prefix step — positions run to prefix_capacity + capacity, the workspace is that launch's)."""
         W, tc, dev = self.W, self.cfg.text_config, self.device
         (H, KV), hd, D = self._llm_heads(), tc.head_dim, tc.hidden_size
         hl = self.decode_hl(B)
         R = 2 * B if hl else B
-        cos, sin = self.rope_tables(torch.arange(capacity))
+        cos, sin = self.rope_tables(torch.arange(prefix_capacity + capacity))
+        ws_elems = (self.ops.decode_shared_workspace_elems(B, H, hd, prefix_capacity, capacity) if prefix_capacity
+                    else self.ops.decode_workspace_elems(B, H, hd, capacity))
         return DecodeState(
             B=B, capacity=capacity, mode=(self.precision, self.decode_precision), layout=self.llm_packed, hl=hl,
             tok=torch.zeros(B, dtype=torch.int64, device=dev), src=torch.arange(B, dtype=torch.int64, device=dev),
@@ -1577,7 +1586,7 @@ class LeopardEngine:
             k_begin=(torch.arange(B, dtype=torch.int32) * capacity).to(dev),
             x=self._empty(B, D, dtype=torch.float32), h=self._empty(R, D), qkv=self._empty(B, (H + 2 * KV) * hd), att=self._empty(R, H * hd),
             gu=self._empty(R, W.llm_ff), hf32=self._empty(B, D, dtype=torch.float32) if hl else None, cos=cos, sin=sin,
-            ws=torch.empty(self.ops.decode_workspace_elems(B, H, hd, capacity), dtype=torch.float32, device=dev),
+            ws=torch.empty(ws_elems, dtype=torch.float32, device=dev),
             temp=torch.ones(B, dtype=torch.float32, device=dev), topk=torch.zeros(B, dtype=torch.int32, device=dev),
             topp=torch.ones(B, dtype=torch.float32, device=dev), seed=torch.zeros(B, dtype=torch.int64, device=dev),
             step=torch.zeros(B, dtype=torch.int32, device=dev))
@@ -1807,10 +1816,65 @@ class LeopardEngine:
         st = states.get(B)
         if st is not None and st.capacity >= need and st.mode == (self.precision, self.decode_precision):
             return st
-        W, tc, dev = self.W, self.cfg.text_config, self.device
-        (H, KV), hd, D = self._llm_heads(), tc.head_dim, tc.hidden_size
         cap = (need + 1023) // 1024 * 1024
         st = self._decode_buffers(B, cap)
+        self._pool_buffers(st)
+        # bounded: a serving process that sees many batch sizes keeps the pools of the two most recent ones (each is B x capacity KV rows)
+        while len(states) >= 2:
+            states.pop(next(iter(states)))
+        states[B] = st
+        return st
+
+    SHARED_OWN_ROWS = 256              # shared-prefix decode: a slot's own rows (question + new tokens) are rounded up to this ...
+    SHARED_PREFIX_ROWS = 1024          # ... and the one prefix copy to this, so that calls of about the same shape reuse one captured step
+
+    def _shared_decode_guard(self, B: int) -> None:
+        """generate_shared(decode="shared"): the shapes lmi_attn_decode_shared serves — anything else is an error, never another path."""
+        tc = self.cfg.text_config
+        H, KV = self._llm_heads()
+        if tc.head_dim != 128:
+            raise NotImplementedError(f"generate_shared(decode='shared'): head_dim {tc.head_dim} is not supported (the shared-prefix decode attention needs 128)")
+        if H != 4 * KV:
+            raise NotImplementedError(f"generate_shared(decode='shared'): {H} query / {KV} KV heads are not supported (the prefix pass packs the 4 "
+                                      "query heads of one KV head into a workgroup: the ratio must be 4)")
+        if not self._batch_decode_supported():
+            raise NotImplementedError("generate_shared(decode='shared'): this shape has no batched decode (lmi_gemm_skinny needs hidden and "
+                                      "feed-forward widths that are multiples of 128)")
+        if B > 32:
+            raise NotImplementedError(f"generate_shared(decode='shared'): {B} sequences in one step (at most 32: one row of a 32-row tile each)")
+
+    def _shared_state(self, B: int, need_own: int, need_prefix: int) -> DecodeState:
+        """The pooled decode state of ``_batch_state`` with the prefix stored ONCE: B slots of own_capacity rows (a sequence's suffix and new
+        tokens) + one prefix buffer of prefix_capacity rows per layer.  Kept per (B, own capacity, prefix capacity) next to the copy states,
+        under the same bound of two retained pools; a later call whose own rows and prefix fit reuses the buffers and the captured step
+        (the prefix length is a device int)."""
+        states = self._batch_states
+        key = ("shared", B)
+        st = states.get(key)
+        if (st is not None and st.capacity >= need_own and st.prefix_capacity >= need_prefix and st.mode == (self.precision, self.decode_precision)):
+            return st
+        tc, dev = self.cfg.text_config, self.device
+        KV, hd = self._llm_heads()[1], tc.head_dim
+        own = (need_own + self.SHARED_OWN_ROWS - 1) // self.SHARED_OWN_ROWS * self.SHARED_OWN_ROWS
+        pcap = (need_prefix + self.SHARED_PREFIX_ROWS - 1) // self.SHARED_PREFIX_ROWS * self.SHARED_PREFIX_ROWS
+        states.pop(key, None)                                          # the pool it replaces goes first: never two of one batch size
+        st = self._decode_buffers(B, own, prefix_capacity=pcap)
+        self._pool_buffers(st)
+        n_layers = len(self.W.llm_layers)
+        st.kp = [torch.zeros(pcap, KV * hd, dtype=self.dtype, device=dev) for _ in range(n_layers)]
+        st.vp = [torch.zeros(pcap, KV * hd, dtype=self.dtype, device=dev) for _ in range(n_layers)]
+        st.prefix_capacity = pcap
+        st.prefix_len = torch.ones(1, dtype=torch.int32, device=dev)
+        while len(states) >= 2:
+            states.pop(next(iter(states)))
+        states[key] = st
+        return st
+
+    def _pool_buffers(self, st: DecodeState) -> None:
+        """The pooled KV slots and the device side of continuous batching of a B-sequence decode state."""
+        W, tc, dev = self.W, self.cfg.text_config, self.device
+        (H, KV), hd, D = self._llm_heads(), tc.head_dim, tc.hidden_size
+        B, cap = st.B, st.capacity
         n_layers = len(W.llm_layers)
         st.k = [torch.zeros(B * cap, KV * hd, dtype=self.dtype, device=dev) for _ in range(n_layers)]
         st.v = [torch.zeros(B * cap, KV * hd, dtype=self.dtype, device=dev) for _ in range(n_layers)]
@@ -1825,11 +1889,6 @@ class LeopardEngine:
         st.eos = torch.full((self.MAX_EOS,), -1, dtype=torch.int64, device=dev)
         st.hist = torch.zeros(self.HIST, B, dtype=torch.int64, device=dev)
         st.hist_pos = torch.zeros(B, dtype=torch.int32, device=dev)
-        # bounded: a serving process that sees many batch sizes keeps the pools of the two most recent ones (each is B x capacity KV rows)
-        while len(states) >= 2:
-            states.pop(next(iter(states)))
-        states[B] = st
-        return st
 
     def _skinny_weights(self):
         """The decode projections + the head in lmi_gemm_skinny's packed (MFMA operand) order — a second copy of the 16-bit LLM weights
@@ -1847,7 +1906,8 @@ class LeopardEngine:
 
     def _skinny_layers(self, st, k_list, v_list, capacity: int, attend):
         """The layer stack of a decode step on the M <= 16 kernels (lmi_gemm_skinny*): st.x (fp32 rows) in, st.x out.  K / V rows are appended
-        to k_list[i] / v_list[i] at row m * capacity + pos[m]; ``attend(i)`` runs layer i's attention from st.qkv into st.att."""
+        to k_list[i] / v_list[i] at row m * capacity + pos[m] (a shared-prefix state: minus *st.prefix_len — the slots hold own rows only);
+        ``attend(i)`` runs layer i's attention from st.qkv into st.att."""
         ops, W, tc = self.ops, self.W, self.cfg.text_config
         (H, KV), hd = self._llm_heads(), tc.head_dim
         eps = tc.rms_norm_eps
@@ -1870,10 +1930,10 @@ class LeopardEngine:
                 ops.rmsnorm(st.x, L.in_norm, st.h, eps)
             if rope_fused:
                 ops.rope_qkv_skinny(qkv_w, st.h, st.qkv, H, KV, hd, st.cos, st.sin, k_list[i], v_list[i], capacity, st.pos, packed,
-                                    rowsq_in=st.sq_b if fold and i > 0 else None, norm_eps=eps, hl=hl)
+                                    rowsq_in=st.sq_b if fold and i > 0 else None, norm_eps=eps, hl=hl, row_bias=st.prefix_len)
             else:
                 ops.gemm_skinny(qkv_w, st.h, st.qkv, 0, packed)
-                ops.rope_qk_rows(st.qkv, H, KV, hd, st.cos, st.sin, k_list[i], v_list[i], capacity, st.pos)
+                ops.rope_qk_rows(st.qkv, H, KV, hd, st.cos, st.sin, k_list[i], v_list[i], capacity, st.pos, row_bias=st.prefix_len)
             attend(i)
             if fold:
                 ops.gemm_skinny(o_w, st.att, st.x, 1, packed, norm_out=st.h, norm_gamma=L.post_norm, rowsq_out=st.sq_a, hl=hl)
@@ -1903,9 +1963,14 @@ class LeopardEngine:
         (H, KV), hd = self._llm_heads(), tc.head_dim
         qw, eps = H * hd, tc.rms_norm_eps
         ops.embed_merge(st.tok, st.src, W.embed, None, st.x)
-        self._skinny_layers(st, st.k, st.v, st.capacity,
-                            lambda i: ops.attention_decode_pool(st.qkv[:, :qw], st.k[i], st.v[i], st.att, st.cu_q, st.k_begin, st.k_len, st.capacity,
-                                                                H, KV, hd, hd ** -0.5, st.ws, window=tc.sliding_window or 0, hl=st.hl))
+        if st.kp is not None:                                         # shared prefix: one walk over the prefix rows serves all B rows
+            attend = lambda i: ops.attention_decode_shared(st.qkv[:, :qw], st.kp[i], st.vp[i], st.prefix_len, st.prefix_capacity, st.k[i], st.v[i],
+                                                           st.att, st.k_begin, st.k_len, st.capacity, H, KV, hd, hd ** -0.5, st.ws, n_seq=st.B,
+                                                           hl=st.hl)
+        else:
+            attend = lambda i: ops.attention_decode_pool(st.qkv[:, :qw], st.k[i], st.v[i], st.att, st.cu_q, st.k_begin, st.k_len, st.capacity,
+                                                         H, KV, hd, hd ** -0.5, st.ws, window=tc.sliding_window or 0, hl=st.hl)
+        self._skinny_layers(st, st.k, st.v, st.capacity, attend)
         # head: one pass over lm_head for all B rows (lmi_lm_head_last streams the 1 GB head once PER row), from a packed copy of the head
         # (1 GB, built on the first batched step: the prefill's and the batch-1 step's head kernels read the nn.Linear layout; B = 8 step
         # 3.29 ms against 3.37 ms from the row-major head in the coalescing lane order)
@@ -1932,16 +1997,17 @@ class LeopardEngine:
         getattr(st, gname).replay()
 
     def _greedy_loop_batch(self, st, prompts: List[List[int]], first: List[int], seq_lens: List[int], max_new_tokens: int, eos,
-                           sampling: Optional[Sequence[SamplingParams]] = None) -> List[List[int]]:
+                           sampling: Optional[Sequence[SamplingParams]] = None, own_lens: Optional[List[int]] = None) -> List[List[int]]:
         """EVAL:448-452 for B sequences at once: every sequence follows exactly the batch-1 rule (emit, stop at eos / max_new_tokens);
-        finished sequences keep riding along in the batch (their slots are private) and are ignored."""
+        finished sequences keep riding along in the batch (their slots are private) and are ignored.  ``own_lens`` (a shared-prefix state):
+        the rows each slot holds — the key count starts there, the position at seq_lens."""
         B = st.B
         outs = [list(p) for p in prompts]
         nxt = [int(f) for f in first]
         done = [False] * B
         st.tok.copy_(torch.tensor(nxt, dtype=torch.int64))
         st.pos.copy_(torch.tensor(seq_lens, dtype=torch.int32))
-        st.k_len.copy_(torch.tensor([s + 1 for s in seq_lens], dtype=torch.int32))
+        st.k_len.copy_(torch.tensor([s + 1 for s in (own_lens or seq_lens)], dtype=torch.int32))
         st.live.fill_(1); st.budget.fill_(1 << 30); st.eos.fill_(-1); st.hist_pos.zero_()      # the host applies the stop rule here
         st.sampling = sampling is not None
         for j, sp in enumerate(sampling or ()):
@@ -2227,19 +2293,28 @@ class LeopardEngine:
     @torch.no_grad()
     def generate_shared(self, prefix_ids: torch.Tensor, tiles: Optional[torch.Tensor], suffixes: Sequence[torch.Tensor],
                         max_new_tokens: int = 128, eos_token_id: Sequence[int] = (128001, 128009),
-                        sampling: Optional[SamplingParams] = None, prefix: Optional[KVCache] = None) -> List[torch.Tensor]:
+                        sampling: Optional[SamplingParams] = None, prefix: Optional[KVCache] = None, decode: str = "copy") -> List[torch.Tensor]:
         """N prompts that share their head — ``prefix_ids`` with all the images (``tiles``) — and differ in a text suffix (the question):
         ONE prefill of the prefix (the vision tower runs once) into a cache of exactly P rows, ONE ``extend`` of the N suffixes, then request
         j's rows — the P prefix rows and its own s_j — are copied into decode slot j and the batch continues through the unchanged batched
         decode (N = 1 and shapes without batched-decode support: the batch-1 cache).  More than MAX_DECODE_BATCH suffixes run in chunks that
         share the one prefix prefill.  Request i samples with ``sampling.for_request(i)``.  Each output is [1, len(prefix_ids) + len(suffix_j)
         + T]: what ``generate`` returns for the concatenated prompt (same rule; tokens can differ on a near tie of the top two logits).
-        The decode slots do NOT share the prefix: each holds its own copy, so the decode pool is B x (P + s + T) rows per layer (a
-        shared-prefix decode attention is the follow-up); what is saved is the prefill — tower and LLM rows fall from N x (P + s) to P + N x s.
+        ``decode`` = "copy" (the default): the decode slots do NOT share the prefix — each holds its own copy, so the decode pool is
+        B x (P + s + T) rows per layer and every step streams the prefix rows once per slot; what is saved is the prefill — tower and LLM rows
+        fall from N x (P + s) to P + N x s.  ``decode`` = "shared": the prefix K / V are stored ONCE in the decode state (one copy out of the
+        caller's cache, which stays untouched) and every step reads them once for the whole chunk (lmi_attn_decode_shared); the slots hold
+        own rows only — prefix_capacity + B x own_capacity rows per layer.  Needs head_dim 128, 4 query heads per KV head and the batched
+        decode (NotImplementedError otherwise: there is no silent fallback); a chunk of one suffix keeps the batch-1 path; under "lo4" /
+        "split" the pair (hl) step serves B <= 8 as it does for "copy", larger chunks decode on the fast step.
         ``prefix``: a cache that a ``prefill(prefix_ids, tiles, cache=prefix)`` has already filled — the prefill is skipped (``tiles`` is not
         read) and, as with ``extend``, the cache is left untouched."""
+        if decode not in ("copy", "shared"):
+            raise ValueError(f"generate_shared: decode must be 'copy' or 'shared', got {decode!r}")
         self._continuation_guard("generate_shared")
         sfx = self._text_suffixes("generate_shared", suffixes)
+        if decode == "shared":
+            self._shared_decode_guard(min(len(sfx), self.MAX_DECODE_BATCH))
         pids = prefix_ids.reshape(1, -1)
         if pids.numel() == 0:
             raise ValueError("generate_shared: the prefix is empty")
@@ -2256,8 +2331,8 @@ class LeopardEngine:
             chunk = sfx[c0:c0 + self.MAX_DECODE_BATCH]
             req = [None if sampling is None else sampling.for_request(c0 + j) for j in range(len(chunk))]
             lens = [int(t.numel()) for t in chunk]
-            decode = max_new_tokens > 1
-            kv = KVCache(self.cfg, sum(lens), self.dtype, self.device) if decode else None
+            stepping = max_new_tokens > 1
+            kv = KVCache(self.cfg, sum(lens), self.dtype, self.device) if stepping else None
             res = self.extend(prefix, chunk, kv_out=kv)
             if sampling is None:
                 first = [self.first_token(res.logits[j]) for j in range(len(chunk))]
@@ -2265,7 +2340,7 @@ class LeopardEngine:
                 first = self.sample_first(res.logits, req)
             prompts = [head + [int(t) for t in ids.reshape(-1).tolist()] for ids in chunk]
             offs = [0] + [int(c) for c in np.cumsum(lens)]
-            if not decode:
+            if not stepping:
                 toks = [p + [f] for p, f in zip(prompts, first)] if max_new_tokens == 1 else prompts
             elif len(chunk) == 1 or not self._batch_decode_supported():
                 toks = []
@@ -2275,6 +2350,14 @@ class LeopardEngine:
                     self._move_kv(kv, offs[j], s, cache.k, cache.v, P)
                     cache.length = P + s
                     toks.append(self._greedy_loop(prompts[j], first[j], cache, max_new_tokens, eos, req[j]))
+            elif decode == "shared":
+                st = self._shared_state(len(chunk), max(lens) + max_new_tokens, P)
+                self._move_kv(prefix, 0, P, st.kp, st.vp, 0)           # the one prefix copy (the captured step reads state-owned memory only)
+                st.prefix_len.fill_(P)
+                for j, s in enumerate(lens):
+                    self._move_kv(kv, offs[j], s, st.k, st.v, j * st.capacity)
+                toks = self._greedy_loop_batch(st, prompts, first, [P + s for s in lens], max_new_tokens, eos,
+                                               None if sampling is None else req, own_lens=lens)
             else:
                 st = self._batch_state(len(chunk), P + max(lens) + max_new_tokens)
                 for j, s in enumerate(lens):

@@ -29,6 +29,13 @@ def _ptr_f32(t: Optional[torch.Tensor], what: str = "bias"):
     return _ptr(t)
 
 
+def _bias_arg(t: torch.Tensor):
+    """``row_bias`` of the rope wrappers: one int32 in device memory (the kernels read const int*)."""
+    if t.dtype != torch.int32 or t.numel() < 1:
+        raise TypeError(f"leopard_amd: row_bias must be an int32 device tensor of one element, got {t.dtype} [{t.numel()}]")
+    return t
+
+
 def lo4_k4(K: int) -> int:
     """Width of the fp4 images of a K-wide operand: K rounded up to the 256-element k-tile of the correction phase."""
     return (K + 255) // 256 * 256
@@ -265,11 +272,39 @@ class Ops:
                                                   workspace.numel() * workspace.element_size(), _DT[q.dtype], self._stream(out)))
         return out
 
-    def rope_qk_rows(self, qkv, n_q_heads, n_kv_heads, head_dim, cos_all, sin_all, k_cache, v_cache, cache_stride, pos_rows):
-        """Batched decode: row s rotated at position pos_rows[s] (int32, device); K / V appended at row s * cache_stride + pos_rows[s]."""
-        self._check(self.lib.lmi_rope_qk_rows(_ptr(qkv), qkv.shape[0], qkv.stride(0), n_q_heads, n_kv_heads, head_dim, _ptr(cos_all),
-                                              _ptr(sin_all), _ptr(k_cache), _ptr(v_cache), k_cache.stride(0), int(cache_stride),
-                                              _ptr(pos_rows), _DT[qkv.dtype], self._stream(qkv)))
+    def attention_decode_shared(self, q, k_prefix, v_prefix, prefix_len, max_prefix_len, k, v, out, k_begin, k_len, max_seqlen_k, n_heads, n_kv_heads,
+                                head_dim, scale, workspace: torch.Tensor, n_seq=None, hl=False):
+        """lmi_attn_decode_shared: decode attention of a batch behind ONE shared prefix.  Row s of q is sequence s; it sees
+        [k_prefix / v_prefix rows 0 .. prefix_len) ; rows k_begin[s] .. k_begin[s] + k_len[s]) of the pooled k / v], all keys visible.
+        ``prefix_len``: int32 device tensor (one element), ``max_prefix_len``: the host bound that fixes the launch geometry.
+        workspace: fp32, decode_shared_workspace_elems().  ``hl``: out has 2 x q rows (lmi_attn_decode_shared_hl)."""
+        if prefix_len.dtype != torch.int32 or k_begin.dtype != torch.int32 or k_len.dtype != torch.int32:
+            raise TypeError("leopard_amd: attention_decode_shared takes int32 device tensors for prefix_len, k_begin and k_len")
+        n_seq = k_len.numel() if n_seq is None else int(n_seq)
+        assert not hl or out.shape[0] == 2 * q.shape[0]
+        self._check((self.lib.lmi_attn_decode_shared_hl if hl else self.lib.lmi_attn_decode_shared)(
+            _ptr(q), _ptr(k_prefix), _ptr(v_prefix), _ptr(prefix_len), int(max_prefix_len), _ptr(k), _ptr(v), _ptr(out), _ptr(k_begin), _ptr(k_len),
+            n_seq, int(max_seqlen_k), q.shape[0], n_heads, n_kv_heads, head_dim, q.stride(0), k_prefix.stride(0), v_prefix.stride(0), k.stride(0),
+            v.stride(0), out.stride(0), float(scale), _ptr(workspace), workspace.numel() * workspace.element_size(), _DT[q.dtype], self._stream(out)))
+        return out
+
+    def decode_shared_workspace_elems(self, q_rows, n_heads, head_dim, max_prefix_len, max_seqlen_k) -> int:
+        n = int(self.lib.lmi_attn_decode_shared_workspace_bytes(q_rows, n_heads, head_dim, int(max_prefix_len), int(max_seqlen_k)))
+        if n < 0:
+            raise RuntimeError("lmi_attn_decode_shared_workspace_bytes: bad arguments")
+        return n // 4
+
+    def rope_qk_rows(self, qkv, n_q_heads, n_kv_heads, head_dim, cos_all, sin_all, k_cache, v_cache, cache_stride, pos_rows, row_bias=None):
+        """Batched decode: row s rotated at position pos_rows[s] (int32, device); K / V appended at row s * cache_stride + pos_rows[s]
+        (``row_bias``, an int32 device tensor of one element: at that row minus row_bias — lmi_rope_qk_rows_biased)."""
+        if row_bias is None:
+            self._check(self.lib.lmi_rope_qk_rows(_ptr(qkv), qkv.shape[0], qkv.stride(0), n_q_heads, n_kv_heads, head_dim, _ptr(cos_all),
+                                                  _ptr(sin_all), _ptr(k_cache), _ptr(v_cache), k_cache.stride(0), int(cache_stride),
+                                                  _ptr(pos_rows), _DT[qkv.dtype], self._stream(qkv)))
+            return qkv
+        self._check(self.lib.lmi_rope_qk_rows_biased(_ptr(qkv), qkv.shape[0], qkv.stride(0), n_q_heads, n_kv_heads, head_dim, _ptr(cos_all),
+                                                     _ptr(sin_all), _ptr(k_cache), _ptr(v_cache), k_cache.stride(0), int(cache_stride),
+                                                     _ptr(pos_rows), _ptr(_bias_arg(row_bias)), _DT[qkv.dtype], self._stream(qkv)))
         return qkv
 
     def gemm_skinny(self, w, x, out, epilogue=0, packed=None, rowsq_in=None, norm_dim=0, norm_eps=0.0, norm_out=None, norm_gamma=None, rowsq_out=None,
@@ -300,12 +335,18 @@ class Ops:
         return out
 
     def rope_qkv_skinny(self, w_rope, x, qkv, n_q_heads, n_kv_heads, head_dim, cos_all, sin_all, k_cache, v_cache, cache_stride, pos_rows, packed=None,
-                        rowsq_in=None, norm_eps=0.0, hl=False):
+                        rowsq_in=None, norm_eps=0.0, hl=False, row_bias=None):
         """lmi_rope_qkv_skinny: batched-decode q|k|v projection with RoPE + KV append in the epilogue (w_rope in rope_permute_rows order);
         rowsq_in: consumer side of the folded RMSNorm.  ``hl``: x holds 2 M rows [T(x); T(x - T(x))] (lmi_rope_qkv_skinny_hl); qkv has M rows."""
         M, K = (x.shape[0] // 2 if hl else x.shape[0]), w_rope.shape[1]
         if packed is None:
             packed = getattr(w_rope, "_lmi_packed", False)
+        if row_bias is not None:                                   # the append row is m * cache_stride + pos_rows[m] - row_bias (int32 device tensor)
+            self._check((self.lib.lmi_rope_qkv_skinny_hl_biased if hl else self.lib.lmi_rope_qkv_skinny_biased)(
+                _ptr(w_rope), _ptr(x), _ptr(qkv), M, n_q_heads, n_kv_heads, head_dim, K, w_rope.stride(0), x.stride(0), qkv.stride(0), int(bool(packed)),
+                _ptr(rowsq_in), 0 if rowsq_in is None else rowsq_in.shape[1], float(norm_eps), _ptr(cos_all), _ptr(sin_all), _ptr(k_cache), _ptr(v_cache),
+                k_cache.stride(0), int(cache_stride), _ptr(pos_rows), _ptr(_bias_arg(row_bias)), _DT[w_rope.dtype], self._stream(qkv)))
+            return qkv
         self._check((self.lib.lmi_rope_qkv_skinny_hl if hl else self.lib.lmi_rope_qkv_skinny)(_ptr(w_rope), _ptr(x), _ptr(qkv), M, n_q_heads, n_kv_heads, head_dim, K, w_rope.stride(0), x.stride(0),
                                                  qkv.stride(0), int(bool(packed)), _ptr(rowsq_in), 0 if rowsq_in is None else rowsq_in.shape[1],
                                                  float(norm_eps), _ptr(cos_all), _ptr(sin_all), _ptr(k_cache), _ptr(v_cache),

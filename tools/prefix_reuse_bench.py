@@ -3,6 +3,7 @@
 with synthetic weights, full depth, the C3 sample (6 x 1344x896: 7187 merged rows, 7139 of them before the question).
 
     python tools/prefix_reuse_bench.py [--precision lo4|fast] [--n 1,4,8,16] [--out profiles/prefix_reuse.json]
+    python tools/prefix_reuse_bench.py --decode shared --n 2,16 --out profiles/prefix_reuse_shared_decode.json
 
 For every N (questions of 48 ids about the same six pages), in ms, the median of --rounds rounds after one warm-up round, both arms in the same
 process, interleaved round by round:
@@ -13,7 +14,11 @@ process, interleaved round by round:
   e  the per-token decode step after either path: (generation with 1 + --decode-tokens tokens - generation with 1 token) / --decode-tokens; the
      same captured step runs on both paths
 and the kernel alone at H 32 / KV 8 / D 128, P = 7139, eight own ranges of 33 .. 300 rows: lmi_attn_prefix_fwd against lmi_attn_varlen_fwd per
-sequence on a materialised [prefix ; own] copy (the copies timed separately).  Times are host clock around work that ends in a device synchronise
+sequence on a materialised [prefix ; own] copy (the copies timed separately).
+--decode shared adds the shared-prefix decode arm (generate_shared(decode="shared"): ONE prefix copy in the decode state, read once per step
+by lmi_attn_decode_shared) next to the copy arm, in the same rounds: its slot fill (d: one prefix copy + N own ranges), its per-token step by
+the same formula as e, the K / V bytes both decode states hold, and the step saving against the byte-count prediction
+(N - 1) x P x 131 072 B / 5.8 TB/s.  Times are host clock around work that ends in a device synchronise
 (the calls read tokens back).  Prints one JSON object (and writes it to --out)."""
 import argparse
 import json
@@ -38,6 +43,7 @@ ap.add_argument("--n", default="1,4,8,16")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--decode-tokens", type=int, default=16)
 ap.add_argument("--layers", default="", help="V,L: reduced depth (a rehearsal; the committed numbers are full depth)")
+ap.add_argument("--decode", choices=["copy", "shared"], default="copy", help="shared: also measure generate_shared(decode='shared') next to the copy arm")
 ap.add_argument("--out", default="")
 args = ap.parse_args()
 if not torch.cuda.is_available():
@@ -78,7 +84,7 @@ P = eng.merged_len(head)
 rng = np.random.default_rng(0)
 result = {"geometry": "Llama-3.1-8B + SigLIP (synthetic weights, fp16)", "depth": f"{cfg.vision_config.num_hidden_layers} + {cfg.text_config.num_hidden_layers} layers",
           "precision": args.precision, "sample": "C3: 6 x 1344x896", "merged_rows": eng.merged_len(ids), "prefix_rows": P, "suffix_ids": SUFFIX,
-          "rounds": args.rounds, "decode_tokens": args.decode_tokens, "per_n": {}}
+          "rounds": args.rounds, "decode_tokens": args.decode_tokens, "decode_arms": ["copy"] + (["shared"] if args.decode == "shared" else []), "per_n": {}}
 T = args.decode_tokens
 for N in [int(x) for x in args.n.split(",")]:
     sfx = [ids[:, -SUFFIX:].to(dev)]
@@ -104,15 +110,25 @@ for N in [int(x) for x in args.n.split(",")]:
             eng._move_kv(prefix, 0, P, st.k, st.v, j * st.capacity)
             eng._move_kv(kv, j * SUFFIX, SUFFIX, st.k, st.v, j * st.capacity + P)
 
+    def fill_shared():
+        st = eng._shared_state(N, SUFFIX + T + 1, P)
+        eng._move_kv(prefix, 0, P, st.kp, st.vp, 0)
+        for j in range(N):
+            eng._move_kv(kv, j * SUFFIX, SUFFIX, st.k, st.v, j * st.capacity)
+
+    shared_arm = args.decode == "shared" and N > 1 and eng._batch_decode_supported()
     prefill_prefix()
     eng.extend(prefix, sfx, kv_out=kv)
-    m = median_of({"a_generate_batch": lambda: eng.generate_batch(full, max_new_tokens=1, eos_token_id=()),
+    extra_m = {"d_slot_fill_shared_decode": fill_shared} if shared_arm else {}
+    extra_d = ({"shared_decode_T": lambda: eng.generate_shared(head, tiles, sfx, max_new_tokens=1 + T, eos_token_id=(), prefix=prefix, decode="shared")}
+               if shared_arm else {})
+    m = median_of({**extra_m, "a_generate_batch": lambda: eng.generate_batch(full, max_new_tokens=1, eos_token_id=()),
                    "shared_total": lambda: eng.generate_shared(head, tiles, sfx, max_new_tokens=1, eos_token_id=()),
                    "b_prefix_prefill": prefill_prefix,
                    "c_extend": lambda: eng.extend(prefix, sfx, kv_out=kv),
                    "d_slot_copies": copies}, args.rounds)
     # the per-token step: the same captured graph after either path
-    d = median_of({"batch_T": lambda: eng.generate_batch(full, max_new_tokens=1 + T, eos_token_id=()),
+    d = median_of({**extra_d, "batch_T": lambda: eng.generate_batch(full, max_new_tokens=1 + T, eos_token_id=()),
                    "shared_T": lambda: eng.generate_shared(head, tiles, sfx, max_new_tokens=1 + T, eos_token_id=(), prefix=prefix),
                    "shared_1": lambda: eng.generate_shared(head, tiles, sfx, max_new_tokens=1, eos_token_id=(), prefix=prefix)}, args.rounds)
     bcd = m["b_prefix_prefill"] + m["c_extend"] + m["d_slot_copies"]
@@ -120,6 +136,21 @@ for N in [int(x) for x in args.n.split(",")]:
     row.update(b_plus_c_plus_d=round(bcd, 3), a_over_bcd=round(m["a_generate_batch"] / bcd, 2),
                e_step_after_generate_batch=round((d["batch_T"] - m["a_generate_batch"]) / T, 3),
                e_step_after_generate_shared=round((d["shared_T"] - d["shared_1"] - m["d_slot_copies"]) / T, 3))
+    if shared_arm:
+        kv_bytes = lambda ts: sum(t.numel() * t.element_size() for t in ts)
+        sc, ss = eng._batch_states[N], eng._batch_states[("shared", N)]
+        step_copy = (d["shared_T"] - d["shared_1"] - m["d_slot_copies"]) / T
+        step_shared = (d["shared_decode_T"] - d["shared_1"] - m["d_slot_fill_shared_decode"]) / T
+        predicted = 1e3 * (N - 1) * P * 131072 / 5.8e12
+        row.update(e_step_shared_decode=round(step_shared, 3), step_saving_ms=round(step_copy - step_shared, 3),
+                   predicted_saving_ms=round(predicted, 3), saving_over_half_predicted=bool(step_copy - step_shared >= 0.5 * predicted),
+                   shared_not_slower_than_copy_by_6_percent=bool(step_shared <= 1.06 * step_copy),
+                   decode_state_kv_bytes_copy=kv_bytes(sc.k + sc.v), decode_state_kv_bytes_shared=kv_bytes(ss.k + ss.v + ss.kp + ss.vp),
+                   decode_state_rows_copy=f"{N} x {sc.capacity}", decode_state_rows_shared=f"{ss.prefix_capacity} + {N} x {ss.capacity}",
+                   hl_step=bool(ss.hl))
+        print(f"N={N}: shared-prefix decode: step {step_shared:.3f} ms against copy {step_copy:.3f} ms (saving {step_copy - step_shared:.3f} ms, predicted "
+              f"{predicted:.3f}); slot fill {m['d_slot_fill_shared_decode']:.2f} ms against {m['d_slot_copies']:.2f} ms; K / V bytes "
+              f"{row['decode_state_kv_bytes_shared']} against {row['decode_state_kv_bytes_copy']}", flush=True)
     result["per_n"][str(N)] = row
     print(f"N={N}: a generate_batch {m['a_generate_batch']:.1f} ms | b prefix prefill {m['b_prefix_prefill']:.1f} + c extend {m['c_extend']:.1f} + d copies "
           f"{m['d_slot_copies']:.1f} = {bcd:.1f} ms (a / (b + c + d) = {row['a_over_bcd']}) | generate_shared end to end {m['shared_total']:.1f} ms | "
