@@ -497,6 +497,23 @@ int lmi_attn_decode_shared_hl(const void* q, const void* k_prefix, const void* v
                               int head_dim, int ldq, int ldkp, int ldvp, int ldk, int ldv, int ldo, float scale, void* workspace, int64_t workspace_bytes,
                               int dtype, void* stream);
 
+/* Row-packed two-range attention: n_rows packed query rows (any number >= 0) that all continue ONE cached key range.  Row r of q attends to
+ *     [k_prefix / v_prefix rows 0 .. prefix_len) ; rows k_begin[r] .. k_begin[r] + k_len[r]) of k / v],
+ * every key of both ranges visible.  Causality inside a continuation is the caller's: row i of a continuation whose new K / V rows start at
+ * row c of k / v gets k_begin = c, k_len = i + 1 (int32 device arrays; the ranges must lie inside k / v).  The lmi_attn_decode_shared launches
+ * with a host prefix length and more than one row block: the prefix pass runs ceil(n_rows / 32) GQA-packed row blocks per (kv head, prefix
+ * split), so the prefix is read once per 32 rows whatever continuation they belong to; the own pass is the pooled split-KV walk with one
+ * workgroup per (row, kv head, split) — it re-reads a continuation's keys once per row, O(s^2) key rows for s rows: meant for short
+ * continuations, correct at any length; one merge over all splits (<= 64) writes the T rows of `out` and, out_f32 != null, the same rows in
+ * fp32 (row stride ldo32) before their rounding — lmi_split_lo4 turns them into T(row) and the fp4 residual image.  The launch geometry
+ * depends on prefix_len, max_k_len (>= every k_len[r]) and the head counts only: a row gets the same bits alone and among any other rows.
+ * Limits (LMI_EINVAL, never a trap): head_dim 128, n_heads == 4 * n_kv_heads, prefix_len >= 1, row strides multiples of 8 (ldo32: 4) and at
+ * least the heads' width, 16-byte aligned pointers, each range's rows within 4 GiB, workspace >= lmi_attn_prefix_rows_workspace_bytes(...). */
+int64_t lmi_attn_prefix_rows_workspace_bytes(int n_rows, int n_heads, int head_dim, int prefix_len, int max_k_len);
+int lmi_attn_prefix_rows(const void* q, const void* k_prefix, const void* v_prefix, int prefix_len, const void* k, const void* v, void* out, float* out_f32,
+                         const int* k_begin, const int* k_len, int n_rows, int max_k_len, int n_heads, int n_kv_heads, int head_dim, int ldq, int ldkp,
+                         int ldvp, int ldk, int ldv, int ldo, int ldo32, float scale, void* workspace, int64_t workspace_bytes, int dtype, void* stream);
+
 /* The KV append at a biased row, for slots that hold only a sequence's own rows behind such a prefix: as lmi_rope_qkv_skinny / _hl and
  * lmi_rope_qk_rows, but row m appends to row m * cache_stride + pos_rows_dev[m] - *row_bias_dev of the pooled caches while it still rotates at
  * pos_rows_dev[m].  row_bias_dev is a device int (one captured step serves prefixes of any length); null = the unbiased call, bit for bit. */

@@ -86,6 +86,8 @@ SIGNATURES = {
     "lmi_attn_decode_shared_workspace_bytes": [_I, _I, _I, _I, _I],      # restype int64 (bind)
     "lmi_attn_decode_shared": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, C.c_int64, _I, _P],
     "lmi_attn_decode_shared_hl": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, C.c_int64, _I, _P],
+    "lmi_attn_prefix_rows_workspace_bytes": [_I, _I, _I, _I, _I],        # restype int64 (bind)
+    "lmi_attn_prefix_rows": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, C.c_int64, _I, _P],
     "lmi_rope_qkv_skinny_biased": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _F, _P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P],
     "lmi_rope_qkv_skinny_hl_biased": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _F, _P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P],
     "lmi_rope_qk_rows_biased": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P],
@@ -117,6 +119,7 @@ def bind(path: str) -> C.CDLL:
     lib.lmi_attn_decode_workspace_bytes.argtypes = [_I, _I, _I, _I]
     lib.lmi_attn_decode_workspace_bytes.restype = C.c_int64
     lib.lmi_attn_decode_shared_workspace_bytes.restype = C.c_int64
+    lib.lmi_attn_prefix_rows_workspace_bytes.restype = C.c_int64
     lib.lmi_llm_prefill_workspace_bytes.argtypes = [C.c_int64, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int64)]
     lib.lmi_llm_prefill_workspace_bytes.restype = C.c_int64
     lib.lmi_vit_workspace_bytes.argtypes = [C.c_int64, _I, _I, _I, _I, C.POINTER(C.c_int64)]

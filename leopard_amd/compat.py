@@ -159,13 +159,49 @@ class LeopardForConditionalGeneration:
     __call__ = forward
 
     @torch.no_grad()
-    def loglikelihood(self, requests: Sequence[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8
-                      ) -> List[Tuple[float, bool]]:
+    def loglikelihood(self, requests: Sequence[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8,
+                      share_prefix: bool = False) -> List[Tuple[float, bool]]:
         """The ``loglikelihood`` contract of VLM evaluation harnesses: [(context_ids [1, S_c], continuation_ids [1, S_t], pixel_values)] ->
         [(sum of log p(continuation | images + context), is_greedy)].  The continuation is appended to the context, the context labelled -100,
         and the requests are scored ``batch_size`` at a time in one packed prefill each (LeopardEngine.score_batch); is_greedy = every
-        continuation token is its row's argmax."""
-        return score_loglikelihood(self.engine, [(c, t, self._as_tiles(p)) for c, t, p in requests], batch_size, self.device)
+        continuation token is its row's argmax.
+        ``share_prefix`` (default False: the path and the bits above): consecutive requests whose ``pixel_values`` are THE SAME OBJECT form a
+        group; the longest common prefix of the group's context ids — cut so that every request keeps at least one context id as its tail —
+        is prefilled once and the group goes through ``loglikelihood_shared``.  A group of one request, or one whose tails would hold an
+        image token, is scored as without the flag.  The results come back in request order."""
+        if not share_prefix:
+            return score_loglikelihood(self.engine, [(c, t, self._as_tiles(p)) for c, t, p in requests], batch_size, self.device)
+        out: List[Tuple[float, bool]] = []
+        i = 0
+        while i < len(requests):
+            j = i + 1
+            while j < len(requests) and requests[j][2] is requests[i][2] and requests[i][2] is not None:
+                j += 1
+            group = requests[i:j]
+            split = shared_context_split([g[0] for g in group], self.config.image_token_index) if len(group) > 1 else None
+            if split is None:
+                out += score_loglikelihood(self.engine, [(c, t, self._as_tiles(p)) for c, t, p in group], batch_size, self.device)
+            else:
+                head, tails = split
+                out += self.loglikelihood_shared(head, group[0][2], [(t, g[1]) for t, g in zip(tails, group)])
+            i = j
+        return out
+
+    @torch.no_grad()
+    def loglikelihood_shared(self, prefix_ids, pixel_values, requests: Sequence[Tuple[torch.Tensor, torch.Tensor]],
+                             attention: Optional[str] = None) -> List[Tuple[float, bool]]:
+        """Rank N continuations over one set of images: ``prefix_ids`` [1, S_p] with ``pixel_values`` is prefilled ONCE (the vision tower runs
+        once), then [(tail_ids [1, t_j >= 0], continuation_ids [1, m_j >= 1])] are scored from its cache together
+        (LeopardEngine.score_shared) -> [(sum of log p(continuation | images + prefix + tail), is_greedy)], what ``loglikelihood`` gives for
+        the concatenated prompts within the tolerances of ``extend``.  ``attention``: "ranges" / "rows" (LeopardEngine.extend); None = the
+        engine's default."""
+        as_ids = lambda t: torch.as_tensor(t).reshape(1, -1).to(torch.int64)
+        res = self.engine.score_shared(as_ids(prefix_ids).to(self.device), self._as_tiles(pixel_values), [(as_ids(t), as_ids(c)) for t, c in requests],
+                                       attention=attention)
+        # one read-back for all requests (every continuation has at least one id, so no result is empty)
+        sums = torch.stack([r.token_logprobs.to(torch.float64).sum() for r in res]).tolist()
+        greedy = torch.stack([(r.argmax == r.target_ids).all() for r in res]).tolist()
+        return [(float(s), bool(g)) for s, g in zip(sums, greedy)]
 
     # ---- EVAL:448-452 ------------------------------------------------------------------------------------------
     def _sampling(self, where: str, unused: dict, do_sample, temperature, top_k, top_p, seed):
@@ -230,6 +266,18 @@ class LeopardForConditionalGeneration:
         samples = [(ids.to(self.device), (lambda f=pix: self._as_tiles(f())) if callable(pix) else self._as_tiles(pix)) for ids, pix in requests]
         return self.engine.generate_stream(samples, batch_size=batch_size, max_new_tokens=max_new_tokens, eos_token_id=eos, stats=stats,
                                            sampling=sp)
+
+
+def shared_context_split(contexts, image_token_index: int):
+    """(head ids [1, h], [tail ids [1, t_j >= 1]]) of the context ids of one group: the longest common prefix, cut so that every context keeps at
+    least one id as its tail.  None when there is no common head or a tail would hold an image token (images belong to the prefix)."""
+    ctx = [torch.as_tensor(c).reshape(-1).to("cpu", torch.int64) for c in contexts]
+    n = min(int(c.numel()) for c in ctx) - 1
+    differ = (torch.stack([c[:n] for c in ctx]) != ctx[0][:n]).any(dim=0).nonzero() if n > 0 else torch.zeros(0, 1)
+    h = int(differ[0]) if differ.numel() else max(n, 0)
+    if h < 1 or any(bool((c[h:] == image_token_index).any()) for c in ctx):
+        return None
+    return ctx[0][:h].reshape(1, -1), [c[h:].reshape(1, -1) for c in ctx]
 
 
 def score_loglikelihood(engine: LeopardEngine, requests, batch_size: int, device) -> List[Tuple[float, bool]]:

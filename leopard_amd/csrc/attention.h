@@ -69,7 +69,8 @@ struct AttnArgs {
     int prefix_len;           // P >= 1 (host integer); the SHARED instantiation: the capacity that bounds the device-resident length
     // Decode with a shared prefix (lmi_attn_decode_shared): two walks write their partials into one workspace and one merge reads them all.
     //   * prefix pass (the SHARED instantiation): ONE key range — k / v are the prefix rows [0, min(k_len[0], prefix_len)), the length in device
-    //     memory — and query row r of q is the current token of sequence r (shared_rows <= 32 of them: one GQA-packed row block);
+    //     memory — and query row r of q is the current token of sequence r (shared_rows of them, n_qblocks = ceil(shared_rows / 32) GQA-packed
+    //     row blocks: one for a decode batch; lmi_attn_prefix_rows packs the rows of many short continuations, k_len == null: prefix_len rows);
     //   * own pass (cu_q == null): one query row per sequence, row s of q, against the pooled rows cu_k[s] .. cu_k[s] + k_len[s]).
     int split_base = 0;       // the partials of this launch are splits split_base .. split_base + n_splits) of the workspace
     int shared_rows = 0;
@@ -371,7 +372,8 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p
     // cu_q == null: one query row per sequence (row seq); SHARED: the one key range of the launch and its shared_rows query rows
     const int q_beg = SHARED ? 0 : (p.cu_q ? p.cu_q[seq] : seq), len_q = SHARED ? p.shared_rows : (p.cu_q ? p.cu_q[seq + 1] - q_beg : 1);
     const int k_beg = SHARED ? 0 : p.cu_k[seq];
-    const int len_k = SHARED ? imax(0, imin(p.k_len[0], p.prefix_len)) : (p.k_len ? p.k_len[seq] : p.cu_k[seq + 1] - k_beg);
+    // SHARED: the prefix length is device-resident (decode: it changes between replays) or, k_len == null, the host integer (lmi_attn_prefix_rows)
+    const int len_k = SHARED ? imax(0, p.k_len ? imin(p.k_len[0], p.prefix_len) : p.prefix_len) : (p.k_len ? p.k_len[seq] : p.cu_k[seq + 1] - k_beg);
     const int bq = pack ? 32 : BQ;                                 // query rows per workgroup
     const int q0 = qb * bq;
     if (q0 >= len_q) return;
@@ -743,7 +745,8 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p
 // result does not depend on timing.
 template <typename T, int D>
 __global__ void __launch_bounds__(256) attn_combine_kernel(const float* part_o, const float* part_ml, T* out, const int* cu_q,
-                                                           int n_seq, int n_heads, int n_splits, int part_rows, int ldo, float scale, int lo_rows) {
+                                                           int n_seq, int n_heads, int n_splits, int part_rows, int ldo, float scale, int lo_rows,
+                                                           float* out32, int ldo32) {
     static_assert(D == 128, "attn_combine_kernel: one float2 per lane");
     __shared__ float wl[64], red[4][D + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -795,6 +798,8 @@ __global__ void __launch_bounds__(256) attn_combine_kernel(const float* part_o, 
         out[(long)row * ldo + head * D + d] = hi;
         // decode precision mode (skinny.h "hl"): the residual of the rounding as a 16-bit row of its own, lo_rows rows further down
         if (lo_rows > 0) out[(long)(row + lo_rows) * ldo + head * D + d] = (T)(y - (float)hi);
+        // lmi_attn_prefix_rows, optional: the fp32 row beside its rounding (lmi_split_lo4 turns it into T(y) — the row above — and the fp4 residual image)
+        if (out32) out32[(long)row * ldo32 + head * D + d] = y;
     }
 }
 

@@ -556,7 +556,7 @@ int attn_decode_impl(AttnArgs a, int n_seq, int max_q, int q_rows, void* out, in
     else LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, a);
     const long items = (long)q_rows * a.n_heads;
     LMI_LAUNCH((attn_combine_kernel<T, 128>), dim3((unsigned)items), dim3(256), 0, stream, (const float*)a.part_o,
-               (const float*)a.part_ml, (T*)out, a.cu_q, n_seq, a.n_heads, a.n_splits, a.part_rows, ldo, a.scale, lo_rows);
+               (const float*)a.part_ml, (T*)out, a.cu_q, n_seq, a.n_heads, a.n_splits, a.part_rows, ldo, a.scale, lo_rows, (float*)nullptr, 0);
     return check_launch("lmi_attn_decode_fwd");
 }
 
@@ -600,9 +600,34 @@ int attn_decode_shared_impl(AttnArgs pre, AttnArgs own, int n_seq, int q_rows, v
     else LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, own);
     const long items = (long)n_seq * own.n_heads;
     LMI_LAUNCH((attn_combine_kernel<T, 128>), dim3((unsigned)items), dim3(256), 0, stream, (const float*)own.part_o, (const float*)own.part_ml, (T*)out,
-               (const int*)nullptr, n_seq, own.n_heads, pre.n_splits + own.n_splits, own.part_rows, ldo, own.scale, lo_rows);
+               (const int*)nullptr, n_seq, own.n_heads, pre.n_splits + own.n_splits, own.part_rows, ldo, own.scale, lo_rows, (float*)nullptr, 0);
     (void)q_rows;
     return check_launch("lmi_attn_decode_shared");
+}
+
+// ---- row-packed two-range attention (lmi_attn_prefix_rows): the three launches above with R packed query rows --------------------------------
+// Prefix pass: ceil(R / 32) GQA-packed row blocks per (kv head, split) — every prefix key is visible to every row, so rows of different
+// continuations share a tile and the prefix is read once per 32 rows.  Own pass: every row is a "sequence" of one query row whose keys are
+// the pooled rows k_begin[r] .. k_begin[r] + k_len[r]) — the caller writes causality into k_len.  One merge over all splits, which also
+// writes the fp32 rows when asked.  The split geometry is decode_shared_splits' (a function of prefix_len, max_k_len and the head counts,
+// never of R or of another row's range): a row alone and the same row among others get the same bits.
+template <typename T>
+int attn_prefix_rows_impl(AttnArgs pre, AttnArgs own, int n_rows, void* out, int ldo, float* out32, int ldo32, void* stream) {
+    static std::atomic<uint64_t> attr_done{0};
+    static std::atomic<uint64_t> attr_done_s{0};
+    static std::atomic<uint64_t> attr_done_p{0};
+    allow_big_lds(attn_fwd_dma_kernel<T, 128, true>, 160 * 1024, attr_done);
+    allow_big_lds(attn_fwd_dma_kernel<T, 128, true, true>, 160 * 1024, attr_done_s);
+    allow_big_lds(attn_fwd_dma_kernel<T, 128, false, true, false, true>, 160 * 1024, attr_done_p);
+    LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, false, true, false, true>), dim3(pre.n_kv_heads * pre.n_splits * pre.n_qblocks), dim3(ATT_THREADS),
+               AttnDmaGeom<128>::SMEM, stream, pre);
+    const dim3 grid(own.n_kv_heads * n_rows * own.n_splits);
+    if (g_attn_stream_kv.load()) LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, own);
+    else LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, own);
+    const long items = (long)n_rows * own.n_heads;
+    LMI_LAUNCH((attn_combine_kernel<T, 128>), dim3((unsigned)items), dim3(256), 0, stream, (const float*)own.part_o, (const float*)own.part_ml, (T*)out,
+               (const int*)nullptr, n_rows, own.n_heads, pre.n_splits + own.n_splits, own.part_rows, ldo, own.scale, 0, out32, ldo32);
+    return check_launch("lmi_attn_prefix_rows");
 }
 
 std::atomic<int> g_skinny_coalesce{1};       // nn.Linear-layout weights of the M <= 16 kernel: 1 = coalescing lane order + ds_bpermute (LAYOUT 2), 0 = MFMA lane order
@@ -1533,6 +1558,58 @@ int lmi_attn_decode_shared_hl(const void* q, const void* k_prefix, const void* v
                               int dtype, void* stream) {
     return attn_decode_shared_entry("lmi_attn_decode_shared_hl", q, k_prefix, v_prefix, prefix_len, max_prefix_len, k, v, out, k_begin, k_len, n_seq, max_seqlen_k,
                                     q_rows, n_heads, n_kv_heads, head_dim, ldq, ldkp, ldvp, ldk, ldv, ldo, scale, workspace, workspace_bytes, dtype, stream, 1);
+}
+
+int64_t lmi_attn_prefix_rows_workspace_bytes(int n_rows, int n_heads, int head_dim, int prefix_len, int max_k_len) {
+    if (n_rows < 0 || n_heads <= 0 || (n_heads & 3) || head_dim <= 0 || prefix_len < 1 || max_k_len < 0) return -1;
+    const SharedSplits g = decode_shared_splits(n_heads / 4, prefix_len, max_k_len);
+    return (int64_t)(g.pre_n + g.own_n) * n_rows * n_heads * (head_dim + 2) * 4;
+}
+
+int lmi_attn_prefix_rows(const void* q, const void* k_prefix, const void* v_prefix, int prefix_len, const void* k, const void* v, void* out, float* out_f32,
+                         const int* k_begin, const int* k_len, int n_rows, int max_k_len, int n_heads, int n_kv_heads, int head_dim, int ldq, int ldkp,
+                         int ldvp, int ldk, int ldv, int ldo, int ldo32, float scale, void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
+    const char* who = "lmi_attn_prefix_rows";
+    if (!q || !k_prefix || !v_prefix || !k || !v || !out || !k_begin || !k_len || !workspace) return fail(LMI_EINVAL, "%s: null pointer", who);
+    if (head_dim != 128) return fail(LMI_EINVAL, "%s: head_dim %d (only 128)", who, head_dim);
+    if (n_heads <= 0 || n_kv_heads <= 0 || n_heads != 4 * n_kv_heads)
+        return fail(LMI_EINVAL, "%s: needs n_heads == 4 * n_kv_heads (a workgroup's 4 waves take the query heads of one kv head), got %d / %d", who, n_heads, n_kv_heads);
+    if (n_rows < 0 || prefix_len < 1 || max_k_len < 0) return fail(LMI_EINVAL, "%s: bad sizes (n_rows >= 0, prefix_len >= 1, max_k_len >= 0)", who);
+    if ((ldq & 7) || (ldkp & 7) || (ldvp & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) || ldq < n_heads * head_dim || ldo < n_heads * head_dim ||
+        ldkp < n_kv_heads * head_dim || ldvp < n_kv_heads * head_dim || ldk < n_kv_heads * head_dim || ldv < n_kv_heads * head_dim ||
+        (out_f32 && ((ldo32 & 3) || ldo32 < n_heads * head_dim)))
+        return fail(LMI_EINVAL, "%s: row strides must be multiples of 8 (fp32 rows: 4) and at least the heads' width", who);
+    if (!aligned16(q) || !aligned16(k_prefix) || !aligned16(v_prefix) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(workspace) ||
+        (out_f32 && !aligned16(out_f32)))
+        return fail(LMI_EINVAL, "%s: alignment", who);
+    if (((long)prefix_len * ldkp + head_dim) * 2 >= (1L << 32) || ((long)prefix_len * ldvp + head_dim) * 2 >= (1L << 32))
+        return fail(LMI_EINVAL, "%s: the prefix K / V rows span >= 4 GiB (prefix_len %d, ldkp %d, ldvp %d)", who, prefix_len, ldkp, ldvp);
+    if (((long)max_k_len * ldk + head_dim) * 2 >= (1L << 32) || ((long)max_k_len * ldv + head_dim) * 2 >= (1L << 32))
+        return fail(LMI_EINVAL, "%s: one row's own K / V range spans >= 4 GiB (max_k_len %d, ldk %d, ldv %d)", who, max_k_len, ldk, ldv);
+    const int64_t need = lmi_attn_prefix_rows_workspace_bytes(n_rows, n_heads, head_dim, prefix_len, max_k_len);
+    if (workspace_bytes < need) return fail(LMI_EINVAL, "%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+    const SharedSplits g = decode_shared_splits(n_kv_heads, prefix_len, max_k_len);
+    const long own_grid = (long)n_kv_heads * n_rows * g.own_n, items = (long)n_rows * n_heads;
+    if (own_grid >= (1L << 31) || items >= (1L << 31)) return fail(LMI_EINVAL, "%s: n_rows %d is more than one launch grid holds", who, n_rows);
+    if (n_rows == 0) return LMI_OK;
+    AttnArgs a;
+    a.q = q; a.out = out; a.cu_q = nullptr; a.cu_k = nullptr;
+    a.out_fp8 = nullptr; a.ldo8 = 0; a.out_fp8_scale = 0.f; a.out_f32 = nullptr; a.ldo32 = 0;
+    a.out4 = nullptr; a.out4_scale = nullptr; a.ld_out4 = a.ld_out4s = 0; a.row_sel = nullptr;
+    a.ldq = ldq; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale; a.window = 0;
+    a.k_prefix = nullptr; a.v_prefix = nullptr; a.ldkp = a.ldvp = 0; a.prefix_len = 0;
+    a.check_k_extent = 0; a.gqa_pack = 1; a.n_qblocks = 1;
+    a.part_rows = n_rows;
+    a.part_o = (float*)workspace;
+    a.part_ml = a.part_o + (size_t)(g.pre_n + g.own_n) * n_rows * n_heads * head_dim;
+    AttnArgs pre = a, own = a;
+    pre.k = k_prefix; pre.v = v_prefix; pre.ldk = ldkp; pre.ldv = ldvp; pre.k_len = nullptr; pre.prefix_len = prefix_len; pre.shared_rows = n_rows;
+    pre.n_qblocks = (n_rows + 31) / 32;
+    pre.n_splits = g.pre_n; pre.split_tiles = g.pre_tiles; pre.split_base = 0;
+    own.k = k; own.v = v; own.ldk = ldk; own.ldv = ldv; own.cu_k = k_begin; own.k_len = k_len;
+    own.n_splits = g.own_n; own.split_tiles = g.own_tiles; own.split_base = g.pre_n;
+    LMI_DISPATCH_T(dtype, (attn_prefix_rows_impl<f16_t>(pre, own, n_rows, out, ldo, out_f32, ldo32, stream)),
+                   (attn_prefix_rows_impl<bf16_t>(pre, own, n_rows, out, ldo, out_f32, ldo32, stream)));
 }
 
 static int gemm_skinny_entry(const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, int packed,

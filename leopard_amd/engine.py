@@ -945,12 +945,15 @@ class LeopardEngine:
             cache.length = S
         return (None, None) if score_rows is not None else self._lm_head(x, last_rows, all_logits)
 
-    def _attend(self, i, qkv, att, cu, max_len, cache, prefix, cu_k, window=None):
+    def _attend(self, i, qkv, att, cu, max_len, cache, prefix, cu_k, window=None, rows_att=None):
         """The attention launch of layer i over the packed q|k|v rows.  ``att``: the 16-bit output rows, or the Lo4Act of the lo4 schedule.
         Default: causal self-attention of the packed sequences.  ``prefix`` (extend): every sequence's keys are [the P cached rows of
         ``prefix`` ; its own rows] — the two-range launch, the prefix read in place.  ``cu_k`` (append): the keys are the rows of ``cache``
         itself, which the q|k|v epilogue has just extended.  ``window`` = (w0, cu_w) (_last_layer_window; one sequence): the queries are
-        the rows w0.. of ``qkv`` (``att``: their output rows), the keys every row — cu_q = cu_w != cu_k = cu, bottom-right causal."""
+        the rows w0.. of ``qkv`` (``att``: their output rows), the keys every row — cu_q = cu_w != cu_k = cu, bottom-right causal.
+        ``rows_att`` (with ``prefix``; _rows_attention): the row-packed launch instead of the two-range one — under lo4 its merge also hands
+        over the fp32 rows and lmi_split_lo4 makes T(o) and the residual image of them (every row selected: _rows_attention_guard)."""
+        from .ops import Lo4Act
         ops, tc = self.ops, self.cfg.text_config
         (H, KV), hd = self._llm_heads(), tc.head_dim
         qw, kw = H * hd, KV * hd
@@ -958,6 +961,15 @@ class LeopardEngine:
         if prefix is not None:
             assert window is None
             P = prefix.length
+            if rows_att is not None:
+                k_begin, k_len, max_k, ws, o32 = rows_att
+                pair = isinstance(att, Lo4Act)
+                assert not pair or att.row_sel is None
+                ops.attention_prefix_rows(q, prefix.k[i][:P], prefix.v[i][:P], P, k, v, att.hi if pair else att, k_begin, k_len, max_k, H, KV, hd,
+                                          hd ** -0.5, ws, out_f32=o32 if pair else None)
+                if pair:
+                    ops.split_lo4(o32, att)
+                return
             ops.attend_prefix(q, k, v, prefix.k[i][:P], prefix.v[i][:P], P, att, cu, max_len, H, KV, hd, hd ** -0.5)
             return
         # (queries, cu_seqlens_q, cu_seqlens_k, longest query sequence) per mode; k / v: the packed rows, or the cache (append)
@@ -1011,14 +1023,14 @@ class LeopardEngine:
         return wq, wkv
 
     def _llm_layers(self, x, cache, cu, cos, sin, max_len, seq_lens=None, all_rows=False, extra_rows=None, prefix=None, cache_pos0=0,
-                    cu_k=None, last_only=False):
+                    cu_k=None, last_only=False, rows_att=None):
         """The Llama / Mistral layers of the fast and of the lo4 schedule: the buffers, the row selection and the weight images are set up per
         schedule, then ONE layer body serves both — the operands choose the entries (ops.linear; fast: 16-bit tensors on the caller-owned
         workspace, lo4: Lo4Acts).  That body is the FUSED schedule: the RMSNorms ride in the GEMM epilogues (under lo4 the producers o_proj /
         down_proj also write the fp4 image of the residual of T(x gamma)), q|k|v + RoPE + KV append is one launch, gate/up's SwiGLU epilogue
         writes down_proj's operand (pair), the attention kernel o_proj's: lo4 adds no launch to the fast schedule.  Where the shapes do not
         allow the fusion the fast schedule runs launch by launch (_llm_layers_unfused); lo4 needs it.
-        ``prefix`` / ``cache_pos0`` / ``cu_k``: continuing from cached rows (extend / append; _attend).  ``last_only`` (llm_prefill; fused
+        ``prefix`` / ``cache_pos0`` / ``cu_k`` / ``rows_att``: continuing from cached rows (extend / append; _attend).  ``last_only`` (llm_prefill; fused
         schedule): only the last row of the one sequence is read afterwards — the last layer projects k | v for every row (the cache needs
         them) and runs q, the attention, o_proj, gate/up and down_proj on the rows of _last_layer_window alone; under lo4 the window also
         holds every selected row, so the selection tables are sliced with the rows.  ``seq_lens`` / ``all_rows`` / ``extra_rows``: what
@@ -1057,7 +1069,7 @@ class LeopardEngine:
             h, qkv, att, gu, sq_a, sq_b = self._carve("llm", total, offs, [(S, D, self.dtype), (S, qw + 2 * kw, self.dtype), (S, qw, self.dtype),
                                                                              (S, W.llm_ff, self.dtype), (S, parts, torch.float32), (S, parts, torch.float32)])
             if not (fused and self.fuse_norm_rope):
-                return self._llm_layers_unfused(x, cache, cu, cos, sin, max_len, (h, qkv, att, gu), prefix, cache_pos0, cu_k)
+                return self._llm_layers_unfused(x, cache, cu, cos, sin, max_len, (h, qkv, att, gu), prefix, cache_pos0, cu_k, rows_att)
         win = self._last_layer_window(S, first_needed) if last_only and prefix is None and cu_k is None else None
         n_layers = len(W.llm_layers)                            # sq_a: partials feeding gate/up; sq_b: feeding the next layer's qkv
         for i, (L, (qkv4, o4, gu4, down4)) in enumerate(zip(W.llm_layers, w4s)):
@@ -1078,7 +1090,7 @@ class LeopardEngine:
                 ops.linear(guw, L.down_w, x[w0:], down4, epilogue=_lib.EPI_RESIDUAL)
                 break
             ops.qkv_rope(h, L.qkv_w_rope, qkv, None if i == 0 else sq_b, tc.rms_norm_eps, cos, sin, kc, vc, cache_pos0, H, KV, hd, qkv4)
-            self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)
+            self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k, rows_att=rows_att)
             ops.linear(att, L.o_w, x, o4, epilogue=_lib.EPI_RESIDUAL, norm_out=h, norm_gamma=L.post_norm, rowsq_out=sq_a)
             ops.linear(h, L.gu_w, gu, gu4, epilogue=_lib.EPI_SWIGLU, rowsq_in=sq_a, norm_dim=D, norm_eps=tc.rms_norm_eps)
             if i + 1 < n_layers:
@@ -1088,7 +1100,7 @@ class LeopardEngine:
             if self.trace:
                 self.trace(f"llm.{i}", x)
 
-    def _llm_layers_unfused(self, x, cache, cu, cos, sin, max_len, bufs, prefix=None, cache_pos0=0, cu_k=None):
+    def _llm_layers_unfused(self, x, cache, cu, cos, sin, max_len, bufs, prefix=None, cache_pos0=0, cu_k=None, rows_att=None):
         """The Llama / Mistral layers of the fast schedule launch by launch, on the workspace buffers ``bufs`` = (h, qkv, att, gu): where the
         shapes do not allow the fused schedule, the tensor-parallel packed prefill and the calibration pass (``_rec``)."""
         ops, W, tc = self.ops, self.W, self.cfg.text_config
@@ -1109,7 +1121,7 @@ class LeopardEngine:
                                  cache.v[i] if cache else None, cache_pos0, H, KV, hd)
             if rec:                                  # operands of the fp8 attention arithmetic (rotated q / k, v)
                 rec(("llm", i, "q"), qkv[:, :qw]); rec(("llm", i, "k"), qkv[:, qw:qw + kw]); rec(("llm", i, "v"), qkv[:, qw + kw:])
-            self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k)
+            self._attend(i, qkv, att, cu, max_len, cache, prefix, cu_k, rows_att=rows_att)
             rec and rec(("llm", i, "att"), att)
             self._row_parallel(att, L.o_w, x, tmp)
             ops.rmsnorm(x, L.post_norm, h, tc.rms_norm_eps)
@@ -2228,8 +2240,174 @@ class LeopardEngine:
             hit = self._geom_cache[key] = (cu, cos, sin, last_rows, cu_list)
         return hit
 
+    ATTENTION_MODES = ("ranges", "rows")
+    # score_shared / loglikelihood_shared with attention=None: "rows" wherever lmi_attn_prefix_rows serves the request, "ranges" elsewhere.  Measured
+    # (profiles/score_shared.json; README "Scoring from a cached prefix"): "rows" is ahead of "ranges" by 2.0 - 3.9 ms at N = 4 and at N = 16, more
+    # than the 0.3 - 0.8 ms round-to-round spread of "ranges" there
+    SCORE_SHARED_ATTENTION = "rows"
+
+    def _attention_mode(self, what: str, attention: str) -> None:
+        if attention not in self.ATTENTION_MODES:
+            raise ValueError(f"{what}: attention must be 'ranges' or 'rows', got {attention!r}")
+
+    def _rows_attention_refusal(self, lens: Sequence[int]) -> Optional[str]:
+        """Why lmi_attn_prefix_rows cannot serve suffixes of these lengths on this model, or None."""
+        (H, KV), hd = self._llm_heads(), self.cfg.text_config.head_dim
+        if hd != 128:
+            return f"attention='rows' needs head_dim 128 (this model: {hd})"
+        if H != 4 * KV:
+            return (f"attention='rows' packs the 4 query heads of one KV head into a workgroup — the ratio must be 4 (this model: {H} query / "
+                    f"{KV} KV heads)")
+        if self.lo4 and any(self.lo4_tail_rows(l) != l for l in lens):
+            return (f"attention='rows' under precision 'lo4' hands its fp32 rows to lmi_split_lo4, which has no row selection: every suffix must "
+                    f"be corrected whole (<= LO4_FULL_BELOW = {self.LO4_FULL_BELOW} rows under lo4_rows = 'auto'); the suffix lengths are {list(lens)}")
+        return None
+
+    def _rows_attention_guard(self, what: str, lens: Sequence[int]) -> None:
+        """attention="rows": the shapes lmi_attn_prefix_rows serves — anything else is an error, never another launch."""
+        why = self._rows_attention_refusal(lens)
+        if why is not None:
+            raise NotImplementedError(f"{what}: {why}")
+
+    def _rows_attention(self, P: int, lens: Sequence[int]):
+        """(k_begin, k_len, max_k_len, workspace, fp32 rows or None) of the row-packed launch over the packed suffix rows: row i of suffix j
+        sees the own rows cu[j] .. cu[j] + i — causality as a key count.  The own pass re-reads a suffix's keys once per row: O(s^2)."""
+        key = ("rows", tuple(int(l) for l in lens))
+        hit = self._geom_cache.get(key)
+        if hit is None:
+            starts = np.cumsum([0] + list(key[1][:-1]))
+            k_begin = np.concatenate([np.full(l, b, dtype=np.int32) for l, b in zip(key[1], starts)])
+            k_len = np.concatenate([np.arange(1, l + 1, dtype=np.int32) for l in key[1]])
+            if len(self._geom_cache) > 64:
+                self._geom_cache.clear()
+            hit = self._geom_cache[key] = (torch.from_numpy(k_begin).to(self.device), torch.from_numpy(k_len).to(self.device))
+        (H, _), hd = self._llm_heads(), self.cfg.text_config.head_dim
+        S, max_k = sum(key[1]), max(key[1])
+        ws = self._empty(self.ops.prefix_rows_workspace_elems(S, H, hd, P, max_k), dtype=torch.float32)
+        o32 = self._empty(S, H * hd, dtype=torch.float32) if self.lo4 else None
+        return hit[0], hit[1], max_k, ws, o32
+
+    def _suffix_targets(self, what: str, sfx: List[torch.Tensor], targets) -> List[np.ndarray]:
+        """Host int64 targets per suffix after the checks that must fail before any launch: one per suffix row, ids in [0, V) or -100."""
+        V, out = self.cfg.text_config.vocab_size, []
+        for j, (ids, t) in enumerate(zip(sfx, targets)):
+            t = torch.as_tensor(t).detach().to("cpu", torch.int64).reshape(-1).numpy()
+            if len(t) != ids.numel():
+                raise ValueError(f"{what}: request {j} has {ids.numel()} suffix ids and {len(t)} targets (one target per suffix row; "
+                                 f"{self.IGNORE_INDEX} = not scored)")
+            bad = np.nonzero((t != self.IGNORE_INDEX) & ((t < 0) | (t >= V)))[0]
+            if len(bad):
+                raise ValueError(f"{what}: targets must be token ids in [0, {V}) or {self.IGNORE_INDEX}: request {j}, targets[{int(bad[0])}] = "
+                                 f"{int(t[bad[0]])}")
+            out.append(t)
+        return out
+
+    def _extend_score_plan(self, what: str, requests, attention: str):
+        """Everything extend_score refuses, checked on the host: (suffixes, their lengths, targets)."""
+        self._attention_mode(what, attention)
+        self._continuation_guard(what)
+        sfx = self._text_suffixes(what, [r[0] for r in requests])
+        tgts = self._suffix_targets(what, sfx, [r[1] for r in requests])
+        lens = [int(t.numel()) for t in sfx]
+        if self.cfg.text_config.head_dim != 128:
+            raise NotImplementedError(f"{what}: the two-range attention launch needs head_dim 128")
+        if attention == "rows":
+            self._rows_attention_guard(what, lens)
+        return sfx, lens, tgts
+
     @torch.no_grad()
-    def extend(self, prefix: KVCache, suffixes: Sequence[torch.Tensor], kv_out: Optional[KVCache] = None) -> ExtendResult:
+    def extend_score(self, prefix: KVCache, requests: Sequence[tuple], attention: str = "ranges", _plan=None) -> List[ScoreResult]:
+        """Score rows that continue ONE cached prefix: ``requests`` = [(suffix_ids [1, s_j], targets [1, s_j])], text ids only.  The suffix
+        rows run as in ``extend`` (positions P .. P + s_j - 1, the prefix read in place and never written — the call can be repeated on the
+        same cache); ``targets[i]`` is the id that suffix row i PREDICTS — already shifted, unlike the ``labels`` of ``score``, which are
+        aligned with the ids and shifted inside — and -100 marks a row that is not scored.  The scored rows go through the chunked head of
+        ``score`` (no [rows, V] tensor beyond one chunk); under lo4 they are in the row selection.  ScoreResult.rows are suffix-relative,
+        seq_len is s_j; a request without a scored row gives the empty result of ``score``.  ``attention``: as ``extend``.  Every error is
+        raised before anything is launched."""
+        sfx, lens, tgts = self._extend_score_plan("extend_score", requests, attention) if _plan is None else _plan
+        P = int(prefix.length)
+        if P < 1:
+            raise ValueError("extend_score: the prefix cache is empty (prefill it first)")
+        rows = [np.nonzero(t != self.IGNORE_INDEX)[0].astype(np.int64) for t in tgts]
+        if not any(len(r) for r in rows):
+            return [self._empty_score(l) for l in lens]
+        offs = np.cumsum([0] + lens[:-1])
+        rows_all = np.concatenate([r + o for r, o in zip(rows, offs)])
+        tgt_all = np.concatenate([t[r] for t, r in zip(tgts, rows)])
+        x = self.embed_merge(torch.cat(sfx, dim=1) if len(sfx) > 1 else sfx[0], None)       # text ids only: one row per id, the suffixes packed
+        cu, cos, sin, _, _ = self._continuation_geometry(P, lens)
+        self.llm_packed
+        self.last_lo4_ranges = None
+        self._llm_layers(x, None, cu, cos, sin, max(lens), lens, extra_rows=rows_all, prefix=prefix,
+                         rows_att=self._rows_attention(P, lens) if attention == "rows" else None)
+        rows_dev = torch.from_numpy(rows_all).to(self.device)
+        tgt_dev = torch.from_numpy(tgt_all).to(self.device)
+        lp, am = self._score_head(x, rows_dev, tgt_dev)
+        out, k = [], 0
+        for r, o, l in zip(rows, offs, lens):
+            m = len(r)
+            if m:
+                loss = (-lp[k:k + m].to(torch.float64).mean()).to(torch.float32)
+                out.append(ScoreResult(loss, lp[k:k + m], am[k:k + m], tgt_dev[k:k + m], rows_dev[k:k + m] - int(o), l))
+            else:
+                out.append(self._empty_score(l))
+            k += m
+        return out
+
+    @torch.no_grad()
+    def score_shared(self, prefix_ids: torch.Tensor, tiles: Optional[torch.Tensor], requests: Sequence[tuple], prefix: Optional[KVCache] = None,
+                     attention: Optional[str] = None) -> List[ScoreResult]:
+        """Rank N continuations of one prompt head: ``prefix_ids`` (with all the images, ``tiles``) is prefilled ONCE — or ``prefix`` is a
+        cache a ``prefill(prefix_ids, tiles, cache=prefix)`` filled, as in ``generate_shared`` — then ONE ``extend_score`` scores
+        ``requests`` = [(tail_ids [1, t_j >= 0], continuation_ids [1, m_j >= 1])]: suffix j is [tail_j ; c_0 .. c_{m-2}], its targets are
+        -100 on every tail row but the last, then c_0 .. c_{m-1} (the last tail row predicts c_0).  When some tail is empty, the last prefix
+        id moves into every suffix and the prefix is prefilled one row shorter (it must be a text token); with ``prefix`` given that row
+        cannot be produced: ValueError.  ``attention``: as ``extend``; None = SCORE_SHARED_ATTENTION ("rows") where that launch serves the model
+        and the suffix lengths, "ranges" where it does not — an explicit "rows" is never replaced.  ScoreResult.rows are suffix-relative."""
+        what = "score_shared"
+        if attention is not None:
+            self._attention_mode(what, attention)
+        self._continuation_guard(what)
+        pids = prefix_ids.reshape(1, -1)
+        if pids.numel() == 0:
+            raise ValueError("score_shared: the prefix is empty")
+        if not len(requests):
+            raise ValueError("score_shared: no request")
+        # the request ids are a few each and every check reads them: they stay on the host until the one embedding launch
+        tails = [torch.as_tensor(r[0]).reshape(1, -1).to("cpu", torch.int64) for r in requests]
+        conts = [torch.as_tensor(r[1]).reshape(1, -1).to("cpu", torch.int64) for r in requests]
+        for j, c in enumerate(conts):
+            if c.numel() == 0:
+                raise ValueError(f"score_shared: request {j} has an empty continuation")
+        if any(t.numel() == 0 for t in tails):
+            if prefix is not None:
+                raise ValueError("score_shared: an empty tail needs the row of the last prefix id, which a given prefix cache no longer "
+                                 "provides (pass that id as the tail and a cache of the shorter prefix)")
+            moved = pids[:, -1:].to("cpu", torch.int64)
+            if int(moved) == self.cfg.image_token_index:
+                raise ValueError("score_shared: with an empty tail the last prefix id moves into the suffixes — it must be a text token")
+            pids = pids[:, :-1]
+            if pids.numel() == 0:
+                raise ValueError("score_shared: the prefix is empty once its last id has moved into the suffixes")
+            tails = [torch.cat([moved, t], dim=1) for t in tails]
+        ext = []
+        for t, c in zip(tails, conts):
+            ign = torch.full((1, t.numel() - 1), self.IGNORE_INDEX, dtype=torch.int64)
+            ext.append((torch.cat([t, c[:, :-1]], dim=1), torch.cat([ign, c], dim=1)))
+        if attention is None:
+            refused = self._rows_attention_refusal([int(e[0].numel()) for e in ext]) if self.SCORE_SHARED_ATTENTION == "rows" else None
+            attention = self.SCORE_SHARED_ATTENTION if refused is None else "ranges"
+        plan = self._extend_score_plan(what, ext, attention)
+        P = self.merged_len(pids)
+        if prefix is None:
+            prefix = KVCache(self.cfg, P, self.dtype, self.device)
+            self.prefill(pids, tiles, cache=prefix)
+        elif prefix.length != P:
+            raise ValueError(f"score_shared: the prefix cache holds {prefix.length} rows, prefix_ids merge to {P}")
+        return self.extend_score(prefix, ext, attention=attention, _plan=plan)
+
+    @torch.no_grad()
+    def extend(self, prefix: KVCache, suffixes: Sequence[torch.Tensor], kv_out: Optional[KVCache] = None, attention: str = "ranges") -> ExtendResult:
         """Run N text-only suffixes ([1, s_j] ids, s_j >= 1) against ONE cached prefix: ``prefix`` is any cache a ``prefill(ids, tiles,
         cache=...)`` filled (P = prefix.length rows).  The suffix rows are embedded, packed, rotated at positions P .. P + s_j - 1 and run
         through the layers of the current precision ("fast" or "lo4"); their attention sees [the P prefix rows ; their own rows] through the
@@ -2237,7 +2415,10 @@ class LeopardEngine:
         packed row offsets (kv_out.length = sum s_j).  ``prefix`` is never written: it can be extended any number of times.  Under lo4 the
         row selection applies to the suffix lengths (a suffix of <= LO4_FULL_BELOW rows is corrected whole); the prefix rows keep the
         schedule of their own prefill.  Not bit-identical to a from-scratch prefill of [prefix ; suffix] (another key-tile partition unless
-        P % 64 == 0, and another row selection); held to the same tolerances against the fp32 oracle."""
+        P % 64 == 0, and another row selection); held to the same tolerances against the fp32 oracle.
+        ``attention``: "ranges" (the default) is that two-range launch; "rows" the row-packed one (lmi_attn_prefix_rows; _rows_attention_guard:
+        NotImplementedError for a shape it cannot serve, never another launch silently) — meant for many SHORT suffixes."""
+        self._attention_mode("extend", attention)
         self._continuation_guard("extend")
         P = int(prefix.length)
         if P < 1:
@@ -2252,12 +2433,14 @@ class LeopardEngine:
                 raise ValueError(f"extend: kv_out holds {kv_out.capacity} rows, the suffixes have {S}")
         if self.cfg.text_config.head_dim != 128:
             raise NotImplementedError("extend: the two-range attention launch needs head_dim 128")
+        if attention == "rows":
+            self._rows_attention_guard("extend", lens)
         xs = [self.embed_merge(t, None) for t in sfx]
         x = torch.cat(xs, dim=0) if len(xs) > 1 else xs[0]
         cu, cos, sin, last_rows, _ = self._continuation_geometry(P, lens)
         self.llm_packed
         self.last_lo4_ranges = None
-        self._llm_layers(x, kv_out, cu, cos, sin, max(lens), lens, prefix=prefix)
+        self._llm_layers(x, kv_out, cu, cos, sin, max(lens), lens, prefix=prefix, rows_att=self._rows_attention(P, lens) if attention == "rows" else None)
         if kv_out is not None:
             kv_out.length = S
         last, _ = self._lm_head(x, last_rows, False)

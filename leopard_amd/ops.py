@@ -294,6 +294,29 @@ class Ops:
             raise RuntimeError("lmi_attn_decode_shared_workspace_bytes: bad arguments")
         return n // 4
 
+    def attention_prefix_rows(self, q, k_prefix, v_prefix, prefix_len, k, v, out, k_begin, k_len, max_k_len, n_heads, n_kv_heads, head_dim, scale,
+                              workspace: torch.Tensor, out_f32=None, n_rows=None):
+        """lmi_attn_prefix_rows: row r of q sees [k_prefix / v_prefix rows 0 .. prefix_len) ; rows k_begin[r] .. k_begin[r] + k_len[r]) of k / v], all
+        keys visible — causality inside a continuation is the caller's k_len.  ``prefix_len``: host int; k_begin / k_len: int32 device tensors;
+        ``max_k_len``: a host bound of k_len that fixes the launch geometry.  workspace: fp32, prefix_rows_workspace_elems().  ``out_f32``: also the
+        fp32 rows before their rounding (split_lo4 makes the residual image of them)."""
+        if k_begin.dtype != torch.int32 or k_len.dtype != torch.int32:
+            raise TypeError("leopard_amd: attention_prefix_rows takes int32 device tensors for k_begin and k_len")
+        n_rows = k_len.numel() if n_rows is None else int(n_rows)
+        assert out_f32 is None or out_f32.dtype == torch.float32
+        self._check(self.lib.lmi_attn_prefix_rows(
+            _ptr(q), _ptr(k_prefix), _ptr(v_prefix), int(prefix_len), _ptr(k), _ptr(v), _ptr(out), _ptr(out_f32), _ptr(k_begin), _ptr(k_len), n_rows,
+            int(max_k_len), n_heads, n_kv_heads, head_dim, q.stride(0), k_prefix.stride(0), v_prefix.stride(0), k.stride(0), v.stride(0), out.stride(0),
+            0 if out_f32 is None else out_f32.stride(0), float(scale), _ptr(workspace), workspace.numel() * workspace.element_size(), _DT[q.dtype],
+            self._stream(out)))
+        return out
+
+    def prefix_rows_workspace_elems(self, n_rows, n_heads, head_dim, prefix_len, max_k_len) -> int:
+        n = int(self.lib.lmi_attn_prefix_rows_workspace_bytes(int(n_rows), n_heads, head_dim, int(prefix_len), int(max_k_len)))
+        if n < 0:
+            raise RuntimeError("lmi_attn_prefix_rows_workspace_bytes: bad arguments")
+        return n // 4
+
     def rope_qk_rows(self, qkv, n_q_heads, n_kv_heads, head_dim, cos_all, sin_all, k_cache, v_cache, cache_stride, pos_rows, row_bias=None):
         """Batched decode: row s rotated at position pos_rows[s] (int32, device); K / V appended at row s * cache_stride + pos_rows[s]
         (``row_bias``, an int32 device tensor of one element: at that row minus row_bias — lmi_rope_qk_rows_biased)."""
