@@ -567,6 +567,21 @@ int lmi_rmsnorm_rows(const float* x, const int64_t* rows, const float* w, void* 
 int lmi_token_logprobs(const float* logits, const int64_t* rows, const int64_t* targets, int n_rows, int vocab, int ld, float* logprob, float* lse,
                        int64_t* argmax, void* stream);
 
+/* Log-probabilities of the tokens a decode step just chose (generate(logprobs=k)): the launch after lmi_decode_advance / lmi_decode_sample
+ * of a step, one workgroup per sequence b, over the RAW fp32 row logits[b] (columns [0, vocab); no temperature, no suppress list):
+ *     lp = logit[tok[b]] - lse,  the bits lmi_token_logprobs gives for that row and target (NaN for tok[b] outside [0, vocab); a NaN in
+ *     the row makes lse NaN);  top_id[j], top_lp[j] for j < top_k = the j-th entry of the row ordered by value descending, id ascending,
+ *     and its logit - lse (NaN entries never enter; -1 / -inf where the row has fewer than top_k non-NaN entries; j >= top_k not written).
+ * Written to ring slot (hist_pos[b] - 1) mod ring_len — the choice kernel has already advanced hist_pos; null hist_pos = slot 0 — of
+ * lp [ring_len, B] fp32, top_id [ring_len, B, LMI_MAX_TOP_LOGPROBS] int32, top_lp [ring_len, B, LMI_MAX_TOP_LOGPROBS] fp32.  tok int64 [B].
+ * The row is read once whatever top_k is; fixed merge order, no atomics: a row's result does not depend on B, its place in the batch or
+ * the run.  No allocation, no host synchronisation, graph-capturable.  LMI_EINVAL: null pointer (hist_pos excepted), top_k outside
+ * [0, LMI_MAX_TOP_LOGPROBS], ring_len < 1, ld_logits < vocab or ld_logits % 4 != 0, logits not 16-byte aligned.
+ * leopard_amd/csrc/decode_logprob.h. */
+#define LMI_MAX_TOP_LOGPROBS 8
+int lmi_decode_logprobs(const float* logits, int B, int vocab, int ld_logits, const int64_t* tok, const int* hist_pos, int ring_len, int top_k,
+                        float* lp, int* top_id, float* top_lp, void* stream);
+
 /* ---- multi-GPU: RCCL collectives over xGMI (SURVEY.md 8(b) "lmi_allgather / lmi_allreduce wrappers over RCCL communicators
  * ... created by lmi_comm_init(rank, nranks, unique_id) and freed by lmi_comm_destroy", 8(e)).  The reference's evaluation is one
  * process per GPU with no collective (run_eval_llava_siglip_multiimg.sh:9-11); its training side states the exchange pattern

@@ -214,58 +214,67 @@ class LeopardForConditionalGeneration:
     @torch.no_grad()
     def generate(self, input_ids, pixel_values=None, attention_mask=None, pad_token_id=None, eos_token_id=None,
                  max_new_tokens: int = 128, use_cache: bool = True, do_sample=None, temperature=None, top_k=None, top_p=None,
-                 seed: Optional[int] = None, **unused):
-        """Greedy (EVAL:448-452), or sampled with ``do_sample=True`` (temperature / top_k / top_p, HF semantics: leopard_amd.sampling)."""
+                 seed: Optional[int] = None, logprobs: Optional[int] = None, **unused):
+        """Greedy (EVAL:448-452), or sampled with ``do_sample=True`` (temperature / top_k / top_p, HF semantics: leopard_amd.sampling).
+        ``logprobs`` = k in 0 .. 8: returns a ``sampling.GenerationLogprobs`` (.sequences, .token_logprobs, .top_token_ids, .top_logprobs,
+        .sequence_logprob) instead of the tensor — computed inside the decode step (LeopardEngine.generate)."""
         sp = self._sampling("generate", unused, do_sample, temperature, top_k, top_p, seed)
         if input_ids.shape[0] != 1:
             raise NotImplementedError("batch 1 per call, as in the reference harness")
         eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
         tiles = self._as_tiles(pixel_values)
-        return self.engine.generate(input_ids.to(self.device), tiles, max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp)
+        out = self.engine.generate(input_ids.to(self.device), tiles, max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp, logprobs=logprobs)
+        return out if logprobs is None else sampling.logprob_outputs(out)[0]
 
 
     @torch.no_grad()
     def generate_batch(self, requests: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], eos_token_id=None,
                        max_new_tokens: int = 128, do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None,
-                       **unused) -> List[torch.Tensor]:
+                       logprobs: Optional[int] = None, **unused):
         """[(input_ids [1, S_in], pixel_values)] -> [LongTensor [1, S_in + T]]: the batched form of ``generate`` (one packed prefill
         for all requests, LeopardEngine.generate_batch).  Not a surface of the reference script — its loop is batch 1 — but of
-        leopard_amd.harness.run_inference(batch_size=...).  Sampling: request i draws with its own seed (SamplingParams.for_request)."""
+        leopard_amd.harness.run_inference(batch_size=...).  Sampling: request i draws with its own seed (SamplingParams.for_request).
+        ``logprobs`` = k: a list of ``sampling.GenerationLogprobs``, one per request, instead of the tensors."""
         sp = self._sampling("generate_batch", unused, do_sample, temperature, top_k, top_p, seed)
         eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
         samples = [(ids.to(self.device), self._as_tiles(pix)) for ids, pix in requests]
-        return self.engine.generate_batch(samples, max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp)
+        out = self.engine.generate_batch(samples, max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp, logprobs=logprobs)
+        return out if logprobs is None else sampling.logprob_outputs(out)
 
 
     @torch.no_grad()
     def generate_shared(self, prefix_ids, pixel_values, suffix_ids_list: Sequence[torch.Tensor], eos_token_id=None, max_new_tokens: int = 128,
                         do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None, decode: str = "copy",
-                        **unused) -> List[torch.Tensor]:
+                        logprobs: Optional[int] = None, **unused):
         """Many questions about one set of images: ``prefix_ids`` [1, S_p] (the chat head and every image group, with ``pixel_values``) is
         prefilled ONCE — the vision tower runs once — and the text-only ``suffix_ids_list`` ([1, s_j] each: question, instruction, tail)
         continue from its cache together (LeopardEngine.generate_shared).  Returns [LongTensor [1, S_p + s_j + T]], each what ``generate``
         returns for the concatenated prompt.  Decoding kwargs as ``generate_batch``; request i draws with its own seed.  Memory: with
         ``decode`` = "copy" (the default) every decode slot holds its own copy of the prefix rows, B x (P + s + T) rows per layer; with
         ``decode`` = "shared" the prefix is stored once and read once per step for the whole batch — about P + B x (s + T) rows per layer
-        (head_dim 128 and 4 query heads per KV head; NotImplementedError otherwise)."""
+        (head_dim 128 and 4 query heads per KV head; NotImplementedError otherwise).  ``logprobs`` = k: a list of
+        ``sampling.GenerationLogprobs`` instead of the tensors (ranking the N answers by ``sequence_logprob`` needs no second pass)."""
         sp = self._sampling("generate_shared", unused, do_sample, temperature, top_k, top_p, seed)
         eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
-        return self.engine.generate_shared(prefix_ids.to(self.device), self._as_tiles(pixel_values), [s.to(self.device) for s in suffix_ids_list],
-                                           max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp, decode=decode)
+        out = self.engine.generate_shared(prefix_ids.to(self.device), self._as_tiles(pixel_values), [s.to(self.device) for s in suffix_ids_list],
+                                          max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp, decode=decode, logprobs=logprobs)
+        return out if logprobs is None else sampling.logprob_outputs(out)
 
     @torch.no_grad()
     def generate_stream(self, requests: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8, eos_token_id=None,
                         max_new_tokens: int = 128, stats: Optional[dict] = None, do_sample=None, temperature=None, top_k=None, top_p=None,
-                        seed: Optional[int] = None, **unused) -> List[torch.Tensor]:
+                        seed: Optional[int] = None, logprobs: Optional[int] = None, **unused):
         """Continuous batching over a list of requests: ``batch_size`` decode slots kept busy (LeopardEngine.generate_stream); the outputs
         come back in request order, each what ``generate`` returns for that request.  Sampling: request i draws with its own seed
-        (SamplingParams.for_request), so its tokens do not depend on ``batch_size``."""
+        (SamplingParams.for_request), so its tokens do not depend on ``batch_size``.  ``logprobs`` = k: a list of
+        ``sampling.GenerationLogprobs`` instead of the tensors."""
         sp = self._sampling("generate_stream", unused, do_sample, temperature, top_k, top_p, seed)
         eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
         # a callable in place of the pixels is called when a slot admits the request (leopard_amd.harness: bounded memory over a shard)
         samples = [(ids.to(self.device), (lambda f=pix: self._as_tiles(f())) if callable(pix) else self._as_tiles(pix)) for ids, pix in requests]
-        return self.engine.generate_stream(samples, batch_size=batch_size, max_new_tokens=max_new_tokens, eos_token_id=eos, stats=stats,
-                                           sampling=sp)
+        out = self.engine.generate_stream(samples, batch_size=batch_size, max_new_tokens=max_new_tokens, eos_token_id=eos, stats=stats,
+                                          sampling=sp, logprobs=logprobs)
+        return out if logprobs is None else sampling.logprob_outputs(out)
 
 
 def shared_context_split(contexts, image_token_index: int):

@@ -18,6 +18,7 @@
 #include "skinny.h"
 #include "sample.h"
 #include "logprob.h"
+#include "decode_logprob.h"
 
 using namespace lmi;
 
@@ -1869,6 +1870,21 @@ int lmi_token_logprobs(const float* logits, const int64_t* rows, const int64_t* 
     a.logits = logits; a.rows = rows; a.targets = targets; a.vocab = vocab; a.ld = ld; a.logprob = logprob; a.lse = lse; a.argmax = argmax;
     LMI_LAUNCH(token_logprobs_kernel, dim3(n_rows), dim3(kLogprobThreads), 0, stream, a);
     return check_launch("lmi_token_logprobs");
+}
+
+int lmi_decode_logprobs(const float* logits, int B, int vocab, int ld_logits, const int64_t* tok, const int* hist_pos, int ring_len, int top_k,
+                        float* lp, int* top_id, float* top_lp, void* stream) {
+    static_assert(kMaxTopLogprobs == LMI_MAX_TOP_LOGPROBS, "the kernel's list length is the header's constant");
+    if (!logits || !tok || !lp || !top_id || !top_lp) return fail(LMI_EINVAL, "lmi_decode_logprobs: null pointer");
+    if (B < 0 || vocab <= 0 || ld_logits < vocab || (ld_logits & 3) || !aligned16(logits) || ring_len < 1 || top_k < 0 || top_k > LMI_MAX_TOP_LOGPROBS)
+        return fail(LMI_EINVAL, "lmi_decode_logprobs: bad argument (B=%d vocab=%d ld_logits=%d ring_len=%d top_k=%d; ld_logits >= vocab, ld_logits %% 4 == 0, "
+                    "16-byte aligned logits, ring_len >= 1, top_k in [0, %d])", B, vocab, ld_logits, ring_len, top_k, LMI_MAX_TOP_LOGPROBS);
+    if (B == 0) return LMI_OK;
+    DecodeLogprobArgs a;
+    a.logits = logits; a.tok = tok; a.hist_pos = hist_pos; a.vocab = vocab; a.ld = ld_logits; a.ring_len = ring_len; a.top_k = top_k; a.B = B;
+    a.lp = lp; a.top_id = top_id; a.top_lp = top_lp;
+    LMI_LAUNCH(decode_logprobs_kernel, dim3(B), dim3(kLogprobThreads), 0, stream, a);
+    return check_launch("lmi_decode_logprobs");
 }
 
 int lmi_gemv_rmsnorm(const void* W, const float* x, const float* norm_weight, float eps, void* out, int N, int K, int ldw,

@@ -104,6 +104,47 @@ class ExtendResult:
     kv_out: Optional["KVCache"] = None           # the suffixes' K / V at packed row offsets (sum of the earlier s_j), when asked for
 
 
+@dataclass
+class GenerateOutput:
+    """What generate / generate_batch / generate_stream / generate_shared return with ``logprobs=k``: the call's usual return value and, per
+    request, the log-probability of every generated token (the one from the prefill logits included) and the k most likely tokens of each
+    step.  All numbers are log-softmax values of the RAW logits row the token was chosen from (lmi_decode_logprobs: no temperature, no
+    suppress list) — what ``score`` / ``loglikelihood`` report on those logits; under sampling or ``suppress_tokens`` the chosen token need
+    not be ``top_ids[t, 0]``."""
+    sequences: object                            # the return value of the call without ``logprobs`` (a tensor, or a list of tensors)
+    token_logprobs: List[torch.Tensor]           # per request fp32 [T]
+    top_ids: List[torch.Tensor]                  # per request int64 [T, k]: value descending, lower id first on ties; -1 = no such entry
+    top_logprobs: List[torch.Tensor]             # per request fp32 [T, k]
+
+    @staticmethod
+    def join(parts: Sequence["GenerateOutput"]) -> "GenerateOutput":
+        """One output of several calls, in order (``sequences`` becomes the list of all their sequences)."""
+        seqs: List[torch.Tensor] = []
+        for p in parts:
+            seqs += p.sequences if isinstance(p.sequences, list) else [p.sequences]
+        return GenerateOutput(seqs, [t for p in parts for t in p.token_logprobs], [t for p in parts for t in p.top_ids],
+                              [t for p in parts for t in p.top_logprobs])
+
+
+class _LogprobRows:
+    """Host side of one request's logprob rows: slices of the rings as they are drained, in token order."""
+    def __init__(self, k: int):
+        self.k, self.lp, self.ti, self.tl = k, [], [], []
+
+    def add(self, lp: torch.Tensor, ti: torch.Tensor, tl: torch.Tensor) -> None:
+        """n more tokens: lp [n], ti / tl [n, 8]."""
+        self.lp.append(lp.reshape(-1)); self.ti.append(ti.reshape(-1, ti.shape[-1])); self.tl.append(tl.reshape(-1, tl.shape[-1]))
+
+    def result(self, T: int):
+        """(token_logprobs [T], top_ids [T, k], top_logprobs [T, k]) of the request's T generated tokens."""
+        k = self.k
+        if not self.lp:
+            return torch.zeros(0), torch.zeros(0, k, dtype=torch.int64), torch.zeros(0, k)
+        lp, ti, tl = torch.cat(self.lp)[:T], torch.cat(self.ti)[:T, :k], torch.cat(self.tl)[:T, :k]
+        assert lp.numel() == T, (lp.numel(), T)
+        return lp.clone(), ti.to(torch.int64), tl.clone()
+
+
 class KVCache:
     def __init__(self, cfg: LeopardConfig, capacity: int, dtype, device, tp_size: int = 1):
         tc = cfg.text_config
@@ -188,9 +229,21 @@ class DecodeState:
     topp: torch.Tensor
     seed: torch.Tensor
     step: torch.Tensor
+    # generate(logprobs=k): the rings lmi_decode_logprobs writes after the choice kernel — ONE buffer of 4-byte words, so that the host
+    # drains all three with one copy: lp fp32 [ring, B], top_id int32 [ring, B, 8], top_lp fp32 [ring, B, 8] are views of it.  ring = HIST
+    # for the pooled states (slot = the step's place in the token history ring), 1 for the batch-1 state (read every step, with the token).
+    # Allocated by the first call with ``logprobs`` (_set_logprobs): a state that never sees one holds what it held before
     sampling: bool = False
+    lp_buf: Optional[torch.Tensor] = None
+    lp: Optional[torch.Tensor] = None
+    top_id: Optional[torch.Tensor] = None
+    top_lp: Optional[torch.Tensor] = None
+    logprobs: Optional[int] = None               # k of the running call: the step also launches lmi_decode_logprobs (``graph_lp`` / ``graph_s_lp``)
     graph: Optional[torch.cuda.CUDAGraph] = None       # the captured greedy step
     graph_s: Optional[torch.cuda.CUDAGraph] = None     # the captured sampled step
+    graph_lp: Optional[torch.cuda.CUDAGraph] = None    # the captured greedy step + logprobs, with top_k = lp_k
+    graph_s_lp: Optional[torch.cuda.CUDAGraph] = None  # the captured sampled step + logprobs, with top_k = lp_k
+    lp_k: Optional[int] = None                   # the top_k the two logprobs graphs were captured with (another k captures them again)
     graph_failed: bool = False                   # tensor parallel: the capture failed once, the step runs eagerly (_decode_run)
     graph_comm_bytes: int = 0                    # tensor parallel: what one replay puts on the links
     sq_a: Optional[torch.Tensor] = None          # folded-norm partials: feeding gate/up ...
@@ -1682,6 +1735,66 @@ class LeopardEngine:
             self.ops.decode_sample(logits, V, st.temp, st.topk, st.topp, st.seed, st.step, st.tok, st.pos, suppress=self.suppress_tokens, **kw)
         else:
             self.ops.decode_advance(logits, V, st.tok, st.pos, suppress=self.suppress_tokens, **kw)
+        if st.logprobs is not None:                                   # generate(logprobs=k): one more launch, after the choice (it reads st.tok)
+            self.ops.decode_logprobs(logits, V, st.tok, st.logprobs, st.lp, st.top_id, st.top_lp, hist_pos=kw.get("hist_pos"))
+
+    # ---- generate(logprobs=k): the host side ----
+    def _logprobs_arg(self, what: str, logprobs: Optional[int]) -> Optional[int]:
+        """Validate ``logprobs`` before anything is launched: None, or k in 0 .. 8 on a single-rank engine."""
+        if logprobs is None:
+            return None
+        K = self.ops.MAX_TOP_LOGPROBS
+        if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)) or not 0 <= int(logprobs) <= K:
+            raise ValueError(f"{what}: logprobs must be None or an int in 0 .. {K}, got {logprobs!r}")
+        if self.tp_size > 1:
+            raise NotImplementedError(f"{what}: logprobs is not supported on tensor-parallel engines (the logprobs launch and its rings belong to "
+                                      "the single-rank decode step; the tensor-parallel step has no captured form with it)")
+        return int(logprobs)
+
+    @staticmethod
+    def _step_graph_name(st) -> str:
+        """Which captured step a state runs: greedy / sampled, each without and with the logprobs launch."""
+        return ("graph_s" if st.sampling else "graph") + ("" if st.logprobs is None else "_lp")
+
+    def _set_logprobs(self, st, k: Optional[int]) -> None:
+        st.logprobs = k
+        if k is not None and st.lp_buf is None:                       # the rings: HIST slots beside a token history ring, else one
+            K, ring = self.ops.MAX_TOP_LOGPROBS, (self.HIST if st.hist is not None else 1)
+            n = ring * st.B
+            st.lp_buf = torch.zeros(n * (1 + 2 * K), dtype=torch.int32, device=self.device)
+            st.lp, st.top_id = st.lp_buf[:n].view(torch.float32).view(ring, st.B), st.lp_buf[n:n * (1 + K)].view(ring, st.B, K)
+            st.top_lp = st.lp_buf[n * (1 + K):].view(torch.float32).view(ring, st.B, K)
+        if k is not None and st.lp_k != k:                            # top_k is a launch argument: the captured logprobs steps hold one value
+            st.graph_lp, st.graph_s_lp, st.lp_k = None, None, k
+
+    def _rings_to_host(self, st):
+        """(lp [ring, B], top_id [ring, B, 8], top_lp [ring, B, 8]) on the host: ONE copy of the state's ring buffer."""
+        buf, n, K = st.lp_buf.to("cpu", copy=True), st.lp.numel(), self.ops.MAX_TOP_LOGPROBS
+        return (buf[:n].view(torch.float32).view(st.lp.shape), buf[n:n * (1 + K)].view(st.top_id.shape),
+                buf[n * (1 + K):].view(torch.float32).view(st.top_lp.shape))
+
+    def first_logprobs(self, logits: torch.Tensor, toks: Sequence[int], k: int):
+        """The logprob rows of the FIRST token of each request, from its prefill / extend logits row ([n, >= vocab] or [vocab]): the same
+        kernel as inside the step, run eagerly (ring of one slot).  Returns host (lp [n], top_id [n, 8], top_lp [n, 8])."""
+        rows = logits.reshape(-1, logits.shape[-1]).float()
+        n, dev, K = rows.shape[0], rows.device, self.ops.MAX_TOP_LOGPROBS
+        V = min(self.cfg.text_config.vocab_size, rows.shape[1])
+        if rows.stride(1) != 1 or rows.stride(0) % 4 or rows.data_ptr() % 16:    # the kernel reads 16-byte aligned rows
+            pad = torch.zeros(n, (rows.shape[1] + 3) // 4 * 4, dtype=torch.float32, device=dev)
+            pad[:, :rows.shape[1]] = rows
+            rows = pad
+        tok = torch.tensor([int(t) for t in toks], dtype=torch.int64).to(dev)
+        lp = torch.zeros(1, n, dtype=torch.float32, device=dev)
+        ti = torch.full((1, n, K), -1, dtype=torch.int32, device=dev)
+        tl = torch.full((1, n, K), float("-inf"), dtype=torch.float32, device=dev)
+        self.ops.decode_logprobs(rows, V, tok, k, lp, ti, tl)
+        return lp[0].cpu(), ti[0].cpu(), tl[0].cpu()
+
+    @staticmethod
+    def _generate_output(sequences, rows: Sequence[_LogprobRows], n_prompt: Sequence[int]) -> GenerateOutput:
+        seqs = sequences if isinstance(sequences, list) else [sequences]
+        res = [r.result(int(s.shape[-1]) - int(p)) for r, s, p in zip(rows, seqs, n_prompt)]
+        return GenerateOutput(sequences, [r[0] for r in res], [r[1] for r in res], [r[2] for r in res])
 
     def sample_first(self, logits: torch.Tensor, params: Sequence["SamplingParams"]) -> List[int]:
         """The first token of each request from its prefill logits row ([n, >= vocab] or [vocab]) through lmi_decode_sample at step 0
@@ -1706,14 +1819,14 @@ class LeopardEngine:
         # CPU tests, host-staged) it cannot be captured and runs eagerly.
         from .dist import RcclComm
         if st.layout != self.llm_packed:                                   # pack_llm_weights / unpack_llm_weights since the capture
-            st.graph, st.graph_s, st.layout = None, None, self.llm_packed
-        gname = "graph_s" if st.sampling else "graph"                      # greedy and sampled steps: one captured graph each
+            st.graph, st.graph_s, st.graph_lp, st.graph_s_lp, st.layout = None, None, None, None, self.llm_packed
+        gname = self._step_graph_name(st)                                  # greedy and sampled steps, without / with logprobs: one captured graph each
         tp_capturable = self.tp_size == 1 or (isinstance(self.comm, RcclComm) and self.tp_decode_graph)
         if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs or not tp_capturable or st.graph_failed:
             self._decode_body(st, cache)
             return
         if getattr(st, gname) is None:
-            restore = (st.tok, st.pos, st.cu_k, st.step)
+            restore = (st.tok, st.pos, st.cu_k, st.step) + (() if st.logprobs is None else (st.lp_buf,))
             body = lambda: self._decode_body(st, cache)
             keep = self._warm_up(body, restore)        # (what the warm-up sends counts in comm.sent_bytes)
             sent0 = self.comm.sent_bytes if self.comm is not None else 0
@@ -1749,7 +1862,7 @@ class LeopardEngine:
     def decode_step(self, token_id: int, cache: KVCache) -> torch.Tensor:
         """Append one token: returns its logits [vocab] (fp32, a view of a static buffer) and advances the cache."""
         st = self._decode_state(cache)
-        st.sampling = False
+        st.sampling, st.logprobs = False, None
         self._decode_seed(st, cache, token_id)
         self._decode_run(st, cache)
         cache.length += 1
@@ -1774,12 +1887,14 @@ class LeopardEngine:
         return int(logits_last.argmax())
 
     def _greedy_loop(self, prompt_ids: List[int], first: int, cache: KVCache, max_new_tokens: int, eos,
-                     sampling: Optional[SamplingParams] = None) -> List[int]:
+                     sampling: Optional[SamplingParams] = None, lpr: Optional[_LogprobRows] = None) -> List[int]:
         """EVAL:448-452 after the prefill: greedy tokens until eos / max_new_tokens; one captured decode step per token.  With ``sampling``
-        the step draws instead (the sampled graph; ``first`` was drawn at step 0)."""
+        the step draws instead (the sampled graph; ``first`` was drawn at step 0).  ``lpr`` (generate(logprobs=k)): the step also writes the
+        token's logprob row, read with one more small copy next to the token's."""
         out, nxt = list(prompt_ids), int(first)
         st = self._decode_state(cache)
         st.sampling = sampling is not None
+        self._set_logprobs(st, None if lpr is None else lpr.k)
         if sampling is not None:
             self._set_sampling(st, 0, sampling)
         self._decode_seed(st, cache, nxt)
@@ -1790,20 +1905,32 @@ class LeopardEngine:
             self._decode_run(st, cache)              # consumes st.tok at st.pos, leaves the next token / position on the device
             cache.length += 1
             nxt = int(st.tok.item())
+            if lpr is not None:
+                lp, ti, tl = self._rings_to_host(st)
+                lpr.add(lp[0], ti[0], tl[0])
         return out
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, tiles: Optional[torch.Tensor], max_new_tokens: int = 128,
-                 eos_token_id: Sequence[int] = (128001, 128009), sampling: Optional[SamplingParams] = None) -> torch.Tensor:
-        """Greedy generation (EVAL:448-452), or sampled with ``sampling``: returns LongTensor [1, S_in + T] on the input device."""
+                 eos_token_id: Sequence[int] = (128001, 128009), sampling: Optional[SamplingParams] = None,
+                 logprobs: Optional[int] = None):
+        """Greedy generation (EVAL:448-452), or sampled with ``sampling``: returns LongTensor [1, S_in + T] on the input device.
+        ``logprobs`` = k in 0 .. 8: returns a ``GenerateOutput`` — that tensor as ``sequences`` plus, for each of the T generated tokens, its
+        log-probability and the k most likely tokens of its step (lmi_decode_logprobs inside the captured step)."""
+        k = self._logprobs_arg("generate", logprobs)
         ids = input_ids.reshape(1, -1)
         S = self.merged_len(ids)
         cache = self._generation_cache((self.tp_padded_len(S) if self.tp_size > 1 else S) + max_new_tokens)
         res = self.prefill(ids, tiles, cache=cache)
         first = self.first_token(res.logits_last) if sampling is None else self.sample_first(res.logits_last, [sampling])[0]
+        lpr = None
+        if k is not None:
+            lpr = _LogprobRows(k)
+            lpr.add(*self.first_logprobs(res.logits_last, [first], k))
         out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], first, cache, max_new_tokens,
-                                set(int(e) for e in eos_token_id), sampling)
-        return torch.tensor([out], dtype=torch.long, device=input_ids.device)
+                                set(int(e) for e in eos_token_id), sampling, lpr)
+        seq = torch.tensor([out], dtype=torch.long, device=input_ids.device)
+        return seq if k is None else self._generate_output(seq, [lpr], [ids.numel()])
 
     # ------------------------------------------------------------------------------------------------
     # f4: batched decode.  B sequences advance together: ONE pass over the weights per step serves B tokens (lmi_gemm_skinny),
@@ -2001,18 +2128,22 @@ class LeopardEngine:
         if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs:
             self._batch_decode_body(st)
             return
-        gname = "graph_s" if st.sampling else "graph"                      # greedy and sampled steps: one captured graph each
+        gname = self._step_graph_name(st)                                  # greedy and sampled steps, without / with logprobs: one captured graph each
         if getattr(st, gname) is None:
             g, _ = self._capture_graph(lambda: self._batch_decode_body(st),
-                                       (st.tok, st.pos, st.k_len, st.live, st.budget, st.hist, st.hist_pos, st.step))
+                                       (st.tok, st.pos, st.k_len, st.live, st.budget, st.hist, st.hist_pos, st.step) +
+                                       (() if st.logprobs is None else (st.lp_buf,)))
             setattr(st, gname, g)
         getattr(st, gname).replay()
 
     def _greedy_loop_batch(self, st, prompts: List[List[int]], first: List[int], seq_lens: List[int], max_new_tokens: int, eos,
-                           sampling: Optional[Sequence[SamplingParams]] = None, own_lens: Optional[List[int]] = None) -> List[List[int]]:
+                           sampling: Optional[Sequence[SamplingParams]] = None, own_lens: Optional[List[int]] = None,
+                           lpr: Optional[Sequence[_LogprobRows]] = None) -> List[List[int]]:
         """EVAL:448-452 for B sequences at once: every sequence follows exactly the batch-1 rule (emit, stop at eos / max_new_tokens);
         finished sequences keep riding along in the batch (their slots are private) and are ignored.  ``own_lens`` (a shared-prefix state):
-        the rows each slot holds — the key count starts there, the position at seq_lens."""
+        the rows each slot holds — the key count starts there, the position at seq_lens.  ``lpr`` (logprobs=k): the steps also fill the
+        logprob rings, drained once per HIST steps (step n writes slot n % HIST); a stopped slot keeps writing and its rows are dropped by
+        the rule that drops its tokens (``_LogprobRows.result`` keeps a request's first T rows)."""
         B = st.B
         outs = [list(p) for p in prompts]
         nxt = [int(f) for f in first]
@@ -2022,8 +2153,15 @@ class LeopardEngine:
         st.k_len.copy_(torch.tensor([s + 1 for s in (own_lens or seq_lens)], dtype=torch.int32))
         st.live.fill_(1); st.budget.fill_(1 << 30); st.eos.fill_(-1); st.hist_pos.zero_()      # the host applies the stop rule here
         st.sampling = sampling is not None
+        self._set_logprobs(st, None if lpr is None else lpr[0].k)
         for j, sp in enumerate(sampling or ()):
             self._set_sampling(st, j, sp)
+        undrained = 0                                                 # steps whose ring slots 0 .. undrained - 1 the host has not read yet
+
+        def drain():
+            lp, ti, tl = self._rings_to_host(st)
+            for j in range(B):
+                lpr[j].add(lp[:undrained, j], ti[:undrained, j], tl[:undrained, j])
         for step in range(max_new_tokens):
             for j in range(B):
                 if not done[j]:
@@ -2034,6 +2172,13 @@ class LeopardEngine:
                 break
             self._batch_decode_run(st)
             nxt = [int(t) for t in st.tok.tolist()]
+            if lpr is not None:
+                undrained += 1
+                if undrained == self.HIST:
+                    drain()
+                    undrained = 0
+        if lpr is not None and undrained:
+            drain()
         return outs
 
     def release_batch_state(self) -> None:
@@ -2050,7 +2195,7 @@ class LeopardEngine:
     @torch.no_grad()
     def generate_stream(self, samples: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8, max_new_tokens: int = 128,
                         eos_token_id: Sequence[int] = (128001, 128009), stats: Optional[dict] = None,
-                        sampling: Optional[SamplingParams] = None) -> List[torch.Tensor]:
+                        sampling: Optional[SamplingParams] = None, logprobs: Optional[int] = None):
         """CONTINUOUS batching (the reference loop EVAL:381-452 is one generate() per record): ``batch_size`` decode slots,
         ONE captured step per token for all of them, and a slot that finishes (eos / max_new_tokens) is handed to the next pending sample
         — prefill of the newcomer, its K / V rows copied into the slot of the pooled cache, five small device writes — without
@@ -2060,13 +2205,17 @@ class LeopardEngine:
         Returns the outputs in input order, each exactly what ``generate`` returns for that sample (same rule; the batched projections sum
         in a different order than the batch-1 GEMVs, so a token can differ only on a near tie of the top two logits).
         ``stats`` (optional dict) receives steps / slot-steps / live slot-steps for occupancy accounting.
-        ``sampling``: sampled decoding; request i draws with ``sampling.for_request(i)``, so its tokens do not depend on ``batch_size``."""
+        ``sampling``: sampled decoding; request i draws with ``sampling.for_request(i)``, so its tokens do not depend on ``batch_size``.
+        ``logprobs`` = k in 0 .. 8: returns a ``GenerateOutput`` (``sequences`` = that list); the logprob rings are read once per window, with
+        the token table."""
+        k = self._logprobs_arg("generate_stream", logprobs)
         assert self.tp_size == 1, "batched generation is a single-rank feature (replicas scale it out)"
         B = max(1, min(int(batch_size), self.MAX_DECODE_BATCH, len(samples)))
         eos = [int(e) for e in eos_token_id]
         req = (lambda i: None) if sampling is None else sampling.for_request
         if B == 1 or not self._batch_decode_supported() or len(eos) > self.MAX_EOS:
-            return [self.generate(ids, t() if callable(t) else t, max_new_tokens, eos, sampling=req(i)) for i, (ids, t) in enumerate(samples)]
+            one = [self.generate(ids, t() if callable(t) else t, max_new_tokens, eos, sampling=req(i), logprobs=k) for i, (ids, t) in enumerate(samples)]
+            return one if k is None else GenerateOutput.join(one)
         need = max(self.merged_len(ids) for ids, _ in samples) + max_new_tokens
         st = self._batch_state(B, need)
         st.eos.fill_(-1)
@@ -2074,6 +2223,8 @@ class LeopardEngine:
             st.eos[:len(eos)].copy_(torch.tensor(eos, dtype=torch.int64))
         st.live.zero_(); st.budget.zero_(); st.pos.zero_(); st.k_len.fill_(1); st.tok.zero_(); st.hist_pos.zero_()
         st.sampling = sampling is not None
+        self._set_logprobs(st, k)
+        lpr = None if k is None else [_LogprobRows(k) for _ in samples]
         eos_set = set(eos)
         outs: List[Optional[List[int]]] = [None] * len(samples)
         slot_sample = [-1] * B                                       # which sample a slot runs (-1: free)
@@ -2098,6 +2249,8 @@ class LeopardEngine:
                 first = self.first_token(res.logits_last) if sampling is None else self.sample_first(res.logits_last, [req(i)])[0]
                 out = [int(t) for t in ids.reshape(-1).tolist()] + [first]
                 outs[i] = out
+                if lpr is not None:
+                    lpr[i].add(*self.first_logprobs(res.logits_last, [first], k))
                 if first in eos_set or max_new_tokens <= 1:
                     continue                                          # finished by the prefill alone
                 self._move_kv(scratch, 0, S, st.k, st.v, j * st.capacity)
@@ -2121,6 +2274,8 @@ class LeopardEngine:
             for _ in range(window):
                 self._batch_decode_run(st)
             toks = st.hist.tolist()                                   # ONE host read per window: [HIST][B]
+            if lpr is not None:                                       # ... and one of the logprob rings, filled slot for slot with it
+                r_lp, r_ti, r_tl = self._rings_to_host(st)
             n_steps += window
             for w in range(window):
                 for j in range(B):
@@ -2131,6 +2286,8 @@ class LeopardEngine:
                     live_steps += 1
                     t = int(toks[w][j])
                     outs[i].append(t)
+                    if lpr is not None:
+                        lpr[i].add(r_lp[w, j], r_ti[w, j], r_tl[w, j])
                     h_budget[j] -= 1
                     if t in eos_set or h_budget[j] <= 0:
                         slot_sample[j] = -1                           # retired: the device froze it at this very step
@@ -2139,12 +2296,13 @@ class LeopardEngine:
                     admit(j)
         if stats is not None:
             stats.update(steps=n_steps, slot_steps=slot_steps, live_slot_steps=live_steps, batch_size=B)
-        return [torch.tensor([o], dtype=torch.long, device=samples[i][0].device) for i, o in enumerate(outs)]
+        seqs = [torch.tensor([o], dtype=torch.long, device=samples[i][0].device) for i, o in enumerate(outs)]
+        return seqs if k is None else self._generate_output(seqs, lpr, [ids.numel() for ids, _ in samples])
 
     @torch.no_grad()
     def generate_batch(self, samples: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], max_new_tokens: int = 128,
                        eos_token_id: Sequence[int] = (128001, 128009), sampling: Optional[SamplingParams] = None,
-                       _first_request: int = 0) -> List[torch.Tensor]:
+                       _first_request: int = 0, logprobs: Optional[int] = None):
         """Several samples per call (batching with per-sample cu_seqlens instead of one sample per generate()):
         ONE packed prefill — all ViT inputs through the tower together, all merged sequences in one varlen causal pass that also
         writes every sample's K/V into a packed cache — then each sample's K/V rows move to its slot of the pooled decode cache (a
@@ -2153,17 +2311,19 @@ class LeopardEngine:
         equivalent, not bit-identical: the first new token comes from the same prefill, the continuation's projections are MFMA tiles with folded
         norms instead of the batch-1 FMA chains, so a greedy choice can differ where the top two logits are within the 16-bit noise (the GPU
         tests assert equality and, where it fails, exactly such a near tie).
-        ``sampling``: sampled decoding, request i with ``sampling.for_request(i)`` (as generate_stream)."""
+        ``sampling``: sampled decoding, request i with ``sampling.for_request(i)`` (as generate_stream).
+        ``logprobs`` = k in 0 .. 8: returns a ``GenerateOutput`` (``sequences`` = that list); the rings are drained once per HIST steps."""
+        k = self._logprobs_arg("generate_batch", logprobs)
         assert self.tp_size == 1, "batched generation is a single-rank feature (replicas scale it out)"
         if len(samples) > self.MAX_DECODE_BATCH:
-            outs = []
-            for i in range(0, len(samples), self.MAX_DECODE_BATCH):
-                outs += self.generate_batch(samples[i:i + self.MAX_DECODE_BATCH], max_new_tokens, eos_token_id, sampling, _first_request + i)
-            return outs
+            outs = [self.generate_batch(samples[i:i + self.MAX_DECODE_BATCH], max_new_tokens, eos_token_id, sampling, _first_request + i, k)
+                    for i in range(0, len(samples), self.MAX_DECODE_BATCH)]
+            return [o for part in outs for o in part] if k is None else GenerateOutput.join(outs)
         req = (lambda i: None) if sampling is None else (lambda i: sampling.for_request(_first_request + i))
         if len(samples) == 1:
             ids, t = samples[0]
-            return [self.generate(ids, t, max_new_tokens, eos_token_id, sampling=req(0))]
+            one = self.generate(ids, t, max_new_tokens, eos_token_id, sampling=req(0), logprobs=k)
+            return [one] if k is None else GenerateOutput.join([one])
         x, seq_lens = self._pack_requests(samples)
         packed = KVCache(self.cfg, sum(seq_lens), self.dtype, self.device)
         last, _ = self.llm_prefill(x, seq_lens, cache=packed)
@@ -2171,6 +2331,13 @@ class LeopardEngine:
             first = [self.first_token(last[j]) for j in range(last.shape[0])]
         else:
             first = self.sample_first(last, [req(j) for j in range(last.shape[0])])
+        lpr = None
+        if k is not None:
+            lpr = [_LogprobRows(k) for _ in samples]
+            f_lp, f_ti, f_tl = self.first_logprobs(last, first, k)
+            for j in range(len(samples)):
+                lpr[j].add(f_lp[j], f_ti[j], f_tl[j])
+        n_prompt = [ids.numel() for ids, _ in samples]
         eos = set(int(e) for e in eos_token_id)
         if not self._batch_decode_supported():
             # shapes the skinny-M kernels do not cover (toy configurations): the samples continue one after another on the engine's ONE
@@ -2181,9 +2348,10 @@ class LeopardEngine:
                 self._move_kv(packed, off, S, cache.k, cache.v, 0)
                 cache.length = S
                 off += S
-                out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], nxt, cache, max_new_tokens, eos, req(j))
+                out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], nxt, cache, max_new_tokens, eos, req(j),
+                                        None if lpr is None else lpr[j])
                 outs.append(torch.tensor([out], dtype=torch.long, device=ids.device))
-            return outs
+            return outs if k is None else self._generate_output(outs, lpr, n_prompt)
         st = self._batch_state(len(samples), max(seq_lens) + max_new_tokens)
         off = 0
         for j, S in enumerate(seq_lens):
@@ -2192,8 +2360,9 @@ class LeopardEngine:
         del packed
         prompts = [[int(t) for t in ids.reshape(-1).tolist()] for ids, _ in samples]
         outs = self._greedy_loop_batch(st, prompts, first, seq_lens, max_new_tokens, eos,
-                                       None if sampling is None else [req(j) for j in range(len(samples))])
-        return [torch.tensor([o], dtype=torch.long, device=ids.device) for o, (ids, _) in zip(outs, samples)]
+                                       None if sampling is None else [req(j) for j in range(len(samples))], lpr=lpr)
+        seqs = [torch.tensor([o], dtype=torch.long, device=ids.device) for o, (ids, _) in zip(outs, samples)]
+        return seqs if k is None else self._generate_output(seqs, lpr, n_prompt)
 
 
     # ------------------------------------------------------------------------------------------------
@@ -2476,7 +2645,8 @@ class LeopardEngine:
     @torch.no_grad()
     def generate_shared(self, prefix_ids: torch.Tensor, tiles: Optional[torch.Tensor], suffixes: Sequence[torch.Tensor],
                         max_new_tokens: int = 128, eos_token_id: Sequence[int] = (128001, 128009),
-                        sampling: Optional[SamplingParams] = None, prefix: Optional[KVCache] = None, decode: str = "copy") -> List[torch.Tensor]:
+                        sampling: Optional[SamplingParams] = None, prefix: Optional[KVCache] = None, decode: str = "copy",
+                        logprobs: Optional[int] = None):
         """N prompts that share their head — ``prefix_ids`` with all the images (``tiles``) — and differ in a text suffix (the question):
         ONE prefill of the prefix (the vision tower runs once) into a cache of exactly P rows, ONE ``extend`` of the N suffixes, then request
         j's rows — the P prefix rows and its own s_j — are copied into decode slot j and the batch continues through the unchanged batched
@@ -2491,7 +2661,10 @@ class LeopardEngine:
         decode (NotImplementedError otherwise: there is no silent fallback); a chunk of one suffix keeps the batch-1 path; under "lo4" /
         "split" the pair (hl) step serves B <= 8 as it does for "copy", larger chunks decode on the fast step.
         ``prefix``: a cache that a ``prefill(prefix_ids, tiles, cache=prefix)`` has already filled — the prefill is skipped (``tiles`` is not
-        read) and, as with ``extend``, the cache is left untouched."""
+        read) and, as with ``extend``, the cache is left untouched.
+        ``logprobs`` = k in 0 .. 8: returns a ``GenerateOutput`` (``sequences`` = that list), in both ``decode`` modes; a request's T counts
+        the tokens after its suffix."""
+        k = self._logprobs_arg("generate_shared", logprobs)
         if decode not in ("copy", "shared"):
             raise ValueError(f"generate_shared: decode must be 'copy' or 'shared', got {decode!r}")
         self._continuation_guard("generate_shared")
@@ -2510,6 +2683,7 @@ class LeopardEngine:
         eos = set(int(e) for e in eos_token_id)
         head = [int(t) for t in pids.reshape(-1).tolist()]
         outs: List[torch.Tensor] = []
+        rows_all: List[_LogprobRows] = []
         for c0 in range(0, len(sfx), self.MAX_DECODE_BATCH):
             chunk = sfx[c0:c0 + self.MAX_DECODE_BATCH]
             req = [None if sampling is None else sampling.for_request(c0 + j) for j in range(len(chunk))]
@@ -2521,6 +2695,13 @@ class LeopardEngine:
                 first = [self.first_token(res.logits[j]) for j in range(len(chunk))]
             else:
                 first = self.sample_first(res.logits, req)
+            lpr = None
+            if k is not None:
+                lpr = [_LogprobRows(k) for _ in chunk]
+                f_lp, f_ti, f_tl = self.first_logprobs(res.logits, first, k)
+                for j in range(len(chunk)):
+                    lpr[j].add(f_lp[j], f_ti[j], f_tl[j])
+                rows_all += lpr
             prompts = [head + [int(t) for t in ids.reshape(-1).tolist()] for ids in chunk]
             offs = [0] + [int(c) for c in np.cumsum(lens)]
             if not stepping:
@@ -2532,7 +2713,7 @@ class LeopardEngine:
                     self._move_kv(prefix, 0, P, cache.k, cache.v, 0)
                     self._move_kv(kv, offs[j], s, cache.k, cache.v, P)
                     cache.length = P + s
-                    toks.append(self._greedy_loop(prompts[j], first[j], cache, max_new_tokens, eos, req[j]))
+                    toks.append(self._greedy_loop(prompts[j], first[j], cache, max_new_tokens, eos, req[j], None if lpr is None else lpr[j]))
             elif decode == "shared":
                 st = self._shared_state(len(chunk), max(lens) + max_new_tokens, P)
                 self._move_kv(prefix, 0, P, st.kp, st.vp, 0)           # the one prefix copy (the captured step reads state-owned memory only)
@@ -2540,13 +2721,13 @@ class LeopardEngine:
                 for j, s in enumerate(lens):
                     self._move_kv(kv, offs[j], s, st.k, st.v, j * st.capacity)
                 toks = self._greedy_loop_batch(st, prompts, first, [P + s for s in lens], max_new_tokens, eos,
-                                               None if sampling is None else req, own_lens=lens)
+                                               None if sampling is None else req, own_lens=lens, lpr=lpr)
             else:
                 st = self._batch_state(len(chunk), P + max(lens) + max_new_tokens)
                 for j, s in enumerate(lens):
                     self._move_kv(prefix, 0, P, st.k, st.v, j * st.capacity)
                     self._move_kv(kv, offs[j], s, st.k, st.v, j * st.capacity + P)
                 toks = self._greedy_loop_batch(st, prompts, first, [P + s for s in lens], max_new_tokens, eos,
-                                               None if sampling is None else req)
+                                               None if sampling is None else req, lpr=lpr)
             outs += [torch.tensor([o], dtype=torch.long, device=ids.device) for o, ids in zip(toks, chunk)]
-        return outs
+        return outs if k is None else self._generate_output(outs, rows_all, [len(head) + int(t.numel()) for t in sfx])

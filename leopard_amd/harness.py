@@ -164,19 +164,31 @@ def shard_result_path(checkpoint: str, shard: int, setting: str, dataset: str) -
 
 
 def run_inference(records: List[dict], model, tokenizer, setting: str = "direct", scorer: Optional[Callable] = None,
-                  device=None, gpu_tiler=None, batch_size: int = 1, stats: Optional[dict] = None) -> List[dict]:
+                  device=None, gpu_tiler=None, batch_size: int = 1, stats: Optional[dict] = None, logprobs: Optional[int] = None) -> List[dict]:
     """The hot loop (EVAL:381-487) over already-sharded records, greedy.  ``gpu_tiler`` (a leopard_amd.gpu_tiler.GpuTiler):
     resize / pad / crop run on the device and the u8 tile stack goes straight to the model (same pixels as the PIL path, bit
     for bit); without it the reference's host pipeline is used.  ``batch_size`` > 1: that many decode SLOTS are kept busy over all
     records (``model.generate_stream``: continuous batching — one captured decode step per token for all slots, a finished record's slot
     goes to the next record at once) instead of the reference's one ``generate`` per record; the rows are the same, in record order.
-    ``stats`` (dict) receives the slot occupancy.  A model without ``generate_stream`` falls back to fixed groups (``generate_batch``)."""
+    ``stats`` (dict) receives the slot occupancy.  A model without ``generate_stream`` falls back to fixed groups (``generate_batch``).
+    ``logprobs`` = k (0 .. 8): the model's generate surfaces run with ``logprobs=k`` and every row additionally carries ``answer_logprob`` (the sum
+    of its answer's token log-probabilities) and ``token_logprobs`` (a list); without it the rows are unchanged."""
     import numpy as np
     import torch
     from .tiler import siglip_preprocess
     rows = []
     size = getattr(getattr(getattr(model, "config", None), "vision_config", None), "image_size", TILE)    # 364 for Leopard
     dev = device if device is not None else model.device
+    lp_kw = {} if logprobs is None else {"logprobs": logprobs}
+
+    def row_of(rec, question, out, enc, n_vit):
+        seq = out if logprobs is None else out.sequences
+        response = tokenizer.batch_decode(seq[:, enc.shape[1]:], skip_special_tokens=True)[0]
+        row = result_row(rec, question, response, n_vit, scorer)
+        if logprobs is not None:
+            row["answer_logprob"] = out.sequence_logprob
+            row["token_logprobs"] = [float(v) for v in out.token_logprobs.tolist()]
+        return row
 
     def prepare(rec):
         if gpu_tiler is not None:
@@ -201,10 +213,9 @@ def run_inference(records: List[dict], model, tokenizer, setting: str = "direct"
             return lambda: prepare(rec)[1]
         kw = generate_kwargs(tokenizer.pad_token_id)
         outs = model.generate_stream([(enc.to(dev), pixels_of(rec)) for rec, (_, _, enc) in zip(records, planned)], batch_size=batch_size,
-                                     eos_token_id=kw["eos_token_id"], max_new_tokens=kw["max_new_tokens"], stats=stats)
+                                     eos_token_id=kw["eos_token_id"], max_new_tokens=kw["max_new_tokens"], stats=stats, **lp_kw)
         for rec, (question, n_vit, enc), out in zip(records, planned, outs):
-            response = tokenizer.batch_decode(out[:, enc.shape[1]:], skip_special_tokens=True)[0]
-            rows.append(result_row(rec, question, response, n_vit, scorer))
+            rows.append(row_of(rec, question, out, enc, n_vit))
         return rows
     for b0 in range(0, len(records), max(1, batch_size)):
         group = records[b0:b0 + max(1, batch_size)]
@@ -214,13 +225,12 @@ def run_inference(records: List[dict], model, tokenizer, setting: str = "direct"
             outs = []
             for s, pixel_values, n_vit, enc in prepared:
                 attn = enc != tokenizer.pad_token_id
-                outs.append(model.generate(enc.to(dev), pixel_values=pixel_values, attention_mask=attn.to(dev), **kw))
+                outs.append(model.generate(enc.to(dev), pixel_values=pixel_values, attention_mask=attn.to(dev), **kw, **lp_kw))
         else:
             outs = model.generate_batch([(enc.to(dev), pixel_values) for _, pixel_values, _, enc in prepared],
-                                        eos_token_id=kw["eos_token_id"], max_new_tokens=kw["max_new_tokens"])
+                                        eos_token_id=kw["eos_token_id"], max_new_tokens=kw["max_new_tokens"], **lp_kw)
         for rec, (s, _, n_vit, enc), out in zip(group, prepared, outs):
-            response = tokenizer.batch_decode(out[:, enc.shape[1]:], skip_special_tokens=True)[0]
-            rows.append(result_row(rec, s.question, response, n_vit, scorer))
+            rows.append(row_of(rec, s.question, out, enc, n_vit))
     return rows
 
 

@@ -28,7 +28,7 @@ import torch
 
 from .checkpoint import CheckpointSource
 from .config import Idefics2Config, PerceiverConfig, TextConfig, VisionConfig
-from .engine import KVCache
+from .engine import KVCache, _LogprobRows
 from .idefics2 import Idefics2Engine, Idefics2Weights, preprocess_image_u8
 from .ops import Ops
 from . import sampling
@@ -269,8 +269,11 @@ class Idefics2ForConditionalGeneration:
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, pixel_values=None, pixel_attention_mask=None, max_new_tokens: int = 128,
                  eos_token_id=None, do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None,
-                 **unused) -> torch.Tensor:
-        """Greedy, or sampled with ``do_sample=True`` (HF semantics, generation_config.json defaults: leopard_amd.sampling)."""
+                 logprobs: Optional[int] = None, **unused):
+        """Greedy, or sampled with ``do_sample=True`` (HF semantics, generation_config.json defaults: leopard_amd.sampling).
+        ``logprobs`` = k in 0 .. 8: returns a ``sampling.GenerationLogprobs`` instead of the tensor (raw-logit log-softmax values: an id of
+        ``suppress_tokens`` may appear among ``top_token_ids``, never as the generated token)."""
+        k = self.engine._logprobs_arg("generate", logprobs)
         sampling.warn_unsupported("generate", unused)
         sp = sampling.resolve(self.generation_defaults, do_sample, temperature, top_k, top_p, seed)
         self.last_decoding = sampling.describe(sp)
@@ -286,5 +289,10 @@ class Idefics2ForConditionalGeneration:
         cache = eng._generation_cache(ids.shape[1] + max_new_tokens)           # one cache + captured decode graph per engine
         res = eng.prefill(ids.to(self.device), images, cache=cache)
         first = eng.first_token(res.logits_last) if sp is None else eng.sample_first(res.logits_last, [sp])[0]
-        out = eng._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], first, cache, max_new_tokens, set(int(e) for e in eos), sp)
-        return torch.tensor([out], dtype=torch.long, device=input_ids.device)
+        lpr = None
+        if k is not None:
+            lpr = _LogprobRows(k)
+            lpr.add(*eng.first_logprobs(res.logits_last, [first], k))
+        out = eng._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], first, cache, max_new_tokens, set(int(e) for e in eos), sp, lpr)
+        seq = torch.tensor([out], dtype=torch.long, device=input_ids.device)
+        return seq if k is None else sampling.logprob_outputs(eng._generate_output(seq, [lpr], [ids.numel()]))[0]

@@ -496,6 +496,22 @@ class Ops:
         self._check(self.lib.lmi_token_logprobs(_ptr(logits), _ptr(rows), _ptr(targets), n, int(vocab), logits.stride(0), _ptr(logprob), _ptr(lse),
                                                 _ptr(argmax), self._stream(logits)))
 
+    MAX_TOP_LOGPROBS = 8               # LMI_MAX_TOP_LOGPROBS: the width of the top_id / top_lp rings
+
+    def decode_logprobs(self, logits, vocab, tok, top_k, lp, top_id, top_lp, hist_pos=None):
+        """lmi_decode_logprobs: after the choice kernel of a decode step, per row b of fp32 ``logits`` [B, ld]: lp = logit[tok[b]] - lse (the
+        bits of ``token_logprobs``) and the row's ``top_k`` (0 .. 8) best (id, logit - lse), written to ring slot (hist_pos[b] - 1) mod
+        ring_len (``hist_pos`` None: slot 0).  tok int64 [B]; lp fp32 [ring_len, B]; top_id int32 / top_lp fp32 [ring_len, B, 8]."""
+        B, K = logits.shape[0], self.MAX_TOP_LOGPROBS
+        ring = lp.shape[0]
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and tok.dtype == torch.int64 and tok.numel() >= B
+        assert lp.dtype == top_lp.dtype == torch.float32 and top_id.dtype == torch.int32
+        assert hist_pos is None or (hist_pos.dtype == torch.int32 and hist_pos.numel() >= B)
+        assert lp.shape == (ring, B) and top_id.shape == top_lp.shape == (ring, B, K) and lp.is_contiguous() and top_id.is_contiguous() and \
+            top_lp.is_contiguous()
+        self._check(self.lib.lmi_decode_logprobs(_ptr(logits), B, int(vocab), logits.stride(0), _ptr(tok), _ptr(hist_pos), ring, int(top_k),
+                                                 _ptr(lp), _ptr(top_id), _ptr(top_lp), self._stream(logits)))
+
     def gemm_ex(self, a, w, out, bias=None, epilogue=EPI_STORE, act=ACT_NONE, rowsq_in=None, norm_dim=0, norm_eps=0.0, norm_out=None,
                 norm_gamma=None, rowsq_out=None):
         """lmi_gemm with the RMSNorm folded in: consumer side (rowsq_in: [M, parts] fp32 partial sums of squares -> rows scaled

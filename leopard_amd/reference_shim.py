@@ -165,6 +165,7 @@ def _llava_class():
             return m
 
         def generate(self, *args, max_new_tokens=128, **kw):
+            # (``logprobs=k`` travels in kw: the return value is then the surface's GenerationLogprobs object)
             out = super().generate(*args, max_new_tokens=_cap_tokens(max_new_tokens), **kw)
             info = getattr(self, "_run_info", None)
             if info is not None and self.last_decoding != getattr(self, "_run_decoding", "greedy"):    # the side file says which rule RAN
@@ -196,6 +197,7 @@ def _idefics2_classes():
             return super().to(_device(device))
 
         def generate(self, *args, max_new_tokens=128, **kw):
+            # (``logprobs=k`` travels in kw, as above)
             out = super().generate(*args, max_new_tokens=_cap_tokens(max_new_tokens), **kw)
             info = getattr(self, "_run_info", None)
             if info is not None and self.last_decoding != getattr(self, "_run_decoding", "greedy"):    # the side file says which rule RAN

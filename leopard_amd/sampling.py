@@ -10,11 +10,12 @@ from __future__ import annotations
 import json
 import os
 import warnings
-from typing import Optional
+from dataclasses import dataclass
+from typing import List, Optional
 
 import torch
 
-from .engine import SamplingParams
+from .engine import GenerateOutput, SamplingParams
 
 HF_DEFAULTS = {"temperature": 1.0, "top_k": 50, "top_p": 1.0}
 SAMPLING_KEYS = ("do_sample", "temperature", "top_k", "top_p")
@@ -24,7 +25,10 @@ UNSUPPORTED = {"num_beams": 1, "num_beam_groups": 1, "penalty_alpha": None, "rep
                "eta_cutoff": 0.0, "num_return_sequences": 1, "diversity_penalty": 0.0, "sequence_bias": None, "guidance_scale": None,
                "low_memory": None, "prompt_lookup_num_tokens": None, "assistant_model": None, "logits_processor": None,
                "min_new_tokens": None, "min_length": None, "renormalize_logits": False, "force_words_ids": None,
-               "constraints": None}
+               "constraints": None,
+               # whole vocabulary rows (or attention maps) per step are not kept: ``logprobs=k`` returns the chosen token's and the top-k
+               # log-probabilities instead
+               "output_scores": False, "output_logits": False, "output_attentions": False}
 
 
 def read_generation_config(path: str) -> dict:
@@ -58,6 +62,28 @@ def resolve(defaults: Optional[dict] = None, do_sample=None, temperature=None, t
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())        # torch's default CPU generator: torch.manual_seed(s) reproduces the run
     return SamplingParams(float(t), int(k), float(p), int(seed))
+
+
+@dataclass
+class GenerationLogprobs:
+    """What a generate() surface returns for one request with ``logprobs=k``: log-softmax values of the raw logits row each token was
+    chosen from — comparable with ``loglikelihood`` / ``forward(labels=)``; under sampling or ``suppress_tokens`` the chosen token need not
+    be ``top_token_ids[t, 0]``."""
+    sequences: torch.Tensor                      # LongTensor [1, S_in + T]: what the call returns without ``logprobs``
+    token_logprobs: torch.Tensor                 # fp32 [T]
+    top_token_ids: torch.Tensor                  # int64 [T, k] (value descending, lower id first on ties; -1 = no such entry)
+    top_logprobs: torch.Tensor                   # fp32 [T, k]
+
+    @property
+    def sequence_logprob(self) -> float:
+        """log p(generated tokens | prompt): the float64 sum of ``token_logprobs``."""
+        return float(self.token_logprobs.to(torch.float64).sum())
+
+
+def logprob_outputs(out: GenerateOutput) -> List[GenerationLogprobs]:
+    """One GenerationLogprobs per request of an engine call made with ``logprobs=k``."""
+    seqs = out.sequences if isinstance(out.sequences, list) else [out.sequences]
+    return [GenerationLogprobs(s, lp, ti, tl) for s, lp, ti, tl in zip(seqs, out.token_logprobs, out.top_ids, out.top_logprobs)]
 
 
 def describe(params: Optional[SamplingParams]) -> str:
