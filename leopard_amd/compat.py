@@ -221,10 +221,10 @@ class LeopardForConditionalGeneration:
         sp = self._sampling("generate", unused, do_sample, temperature, top_k, top_p, seed)
         if input_ids.shape[0] != 1:
             raise NotImplementedError("batch 1 per call, as in the reference harness")
-        eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
         tiles = self._as_tiles(pixel_values)
-        out = self.engine.generate(input_ids.to(self.device), tiles, max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp, logprobs=logprobs)
-        return out if logprobs is None else sampling.logprob_outputs(out)[0]
+        out = self.engine.generate(input_ids.to(self.device), tiles, max_new_tokens=max_new_tokens, eos_token_id=_eos_list(eos_token_id), sampling=sp,
+                                   logprobs=logprobs)
+        return _with_logprobs(out, logprobs, one=True)
 
 
     @torch.no_grad()
@@ -236,10 +236,10 @@ class LeopardForConditionalGeneration:
         leopard_amd.harness.run_inference(batch_size=...).  Sampling: request i draws with its own seed (SamplingParams.for_request).
         ``logprobs`` = k: a list of ``sampling.GenerationLogprobs``, one per request, instead of the tensors."""
         sp = self._sampling("generate_batch", unused, do_sample, temperature, top_k, top_p, seed)
-        eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
         samples = [(ids.to(self.device), self._as_tiles(pix)) for ids, pix in requests]
-        out = self.engine.generate_batch(samples, max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp, logprobs=logprobs)
-        return out if logprobs is None else sampling.logprob_outputs(out)
+        out = self.engine.generate_batch(samples, max_new_tokens=max_new_tokens, eos_token_id=_eos_list(eos_token_id), sampling=sp,
+                                         logprobs=logprobs)
+        return _with_logprobs(out, logprobs)
 
 
     @torch.no_grad()
@@ -255,10 +255,10 @@ class LeopardForConditionalGeneration:
         (head_dim 128 and 4 query heads per KV head; NotImplementedError otherwise).  ``logprobs`` = k: a list of
         ``sampling.GenerationLogprobs`` instead of the tensors (ranking the N answers by ``sequence_logprob`` needs no second pass)."""
         sp = self._sampling("generate_shared", unused, do_sample, temperature, top_k, top_p, seed)
-        eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
         out = self.engine.generate_shared(prefix_ids.to(self.device), self._as_tiles(pixel_values), [s.to(self.device) for s in suffix_ids_list],
-                                          max_new_tokens=max_new_tokens, eos_token_id=eos, sampling=sp, decode=decode, logprobs=logprobs)
-        return out if logprobs is None else sampling.logprob_outputs(out)
+                                          max_new_tokens=max_new_tokens, eos_token_id=_eos_list(eos_token_id), sampling=sp, decode=decode,
+                                          logprobs=logprobs)
+        return _with_logprobs(out, logprobs)
 
     @torch.no_grad()
     def generate_stream(self, requests: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8, eos_token_id=None,
@@ -269,12 +269,25 @@ class LeopardForConditionalGeneration:
         (SamplingParams.for_request), so its tokens do not depend on ``batch_size``.  ``logprobs`` = k: a list of
         ``sampling.GenerationLogprobs`` instead of the tensors."""
         sp = self._sampling("generate_stream", unused, do_sample, temperature, top_k, top_p, seed)
-        eos = eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
         # a callable in place of the pixels is called when a slot admits the request (leopard_amd.harness: bounded memory over a shard)
         samples = [(ids.to(self.device), (lambda f=pix: self._as_tiles(f())) if callable(pix) else self._as_tiles(pix)) for ids, pix in requests]
-        out = self.engine.generate_stream(samples, batch_size=batch_size, max_new_tokens=max_new_tokens, eos_token_id=eos, stats=stats,
-                                          sampling=sp, logprobs=logprobs)
-        return out if logprobs is None else sampling.logprob_outputs(out)
+        out = self.engine.generate_stream(samples, batch_size=batch_size, max_new_tokens=max_new_tokens, eos_token_id=_eos_list(eos_token_id),
+                                          stats=stats, sampling=sp, logprobs=logprobs)
+        return _with_logprobs(out, logprobs)
+
+
+def _eos_list(eos_token_id) -> list:
+    """HF's ``eos_token_id`` (None, one id, or a list / tuple of ids) as the engine's sequence of ids."""
+    return eos_token_id if isinstance(eos_token_id, (list, tuple)) else ([] if eos_token_id is None else [eos_token_id])
+
+
+def _with_logprobs(out, logprobs, one: bool = False):
+    """An engine generation call's return value as the surface returns it: unchanged without ``logprobs``, else one
+    ``sampling.GenerationLogprobs`` per request (``one``: that of the only request)."""
+    if logprobs is None:
+        return out
+    res = sampling.logprob_outputs(out)
+    return res[0] if one else res
 
 
 def shared_context_split(contexts, image_token_index: int):

@@ -21,7 +21,7 @@ import contextlib
 import gc
 import math
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -223,7 +223,7 @@ class DecodeState:
     sin: torch.Tensor
     ws: torch.Tensor                             # decode attention workspace (lmi_decode_workspace_elems)
     # per-row sampling parameters in device memory: written before a replay, read by the captured step, so new parameters never need a
-    # new capture.  ``sampling`` selects which of the two captured steps runs (``graph`` / ``graph_s``)
+    # new capture.  ``sampling`` selects which captured step runs (``graphs``)
     temp: torch.Tensor
     topk: torch.Tensor
     topp: torch.Tensor
@@ -238,11 +238,10 @@ class DecodeState:
     lp: Optional[torch.Tensor] = None
     top_id: Optional[torch.Tensor] = None
     top_lp: Optional[torch.Tensor] = None
-    logprobs: Optional[int] = None               # k of the running call: the step also launches lmi_decode_logprobs (``graph_lp`` / ``graph_s_lp``)
-    graph: Optional[torch.cuda.CUDAGraph] = None       # the captured greedy step
-    graph_s: Optional[torch.cuda.CUDAGraph] = None     # the captured sampled step
-    graph_lp: Optional[torch.cuda.CUDAGraph] = None    # the captured greedy step + logprobs, with top_k = lp_k
-    graph_s_lp: Optional[torch.cuda.CUDAGraph] = None  # the captured sampled step + logprobs, with top_k = lp_k
+    logprobs: Optional[int] = None               # k of the running call: the step also launches lmi_decode_logprobs
+    # the captured steps (LeopardEngine._run_step), keyed by (sampling, with logprobs): greedy / sampled, each without and with the logprobs
+    # launch — the latter two with top_k = lp_k
+    graphs: dict = field(default_factory=dict)
     lp_k: Optional[int] = None                   # the top_k the two logprobs graphs were captured with (another k captures them again)
     graph_failed: bool = False                   # tensor parallel: the capture failed once, the step runs eagerly (_decode_run)
     graph_comm_bytes: int = 0                    # tensor parallel: what one replay puts on the links
@@ -1558,6 +1557,13 @@ class LeopardEngine:
         for i in range(len(src.k)):
             self.ops.kv_append(src.k[i][begin:begin + S], src.v[i][begin:begin + S], k_dst[i], v_dst[i], row0)
 
+    def _load_rows(self, pieces: Sequence[Tuple[KVCache, int, int]], k_dst: List[torch.Tensor], v_dst: List[torch.Tensor], row0: int) -> None:
+        """Fill a decode slot: the row ranges ``pieces`` = [(cache, begin, n)] copied back to back from row ``row0`` of ``k_dst`` / ``v_dst``
+        on (a shared prefix's rows, then the request's own)."""
+        for src, begin, n in pieces:
+            self._move_kv(src, begin, n, k_dst, v_dst, row0)
+            row0 += n
+
     def _score_head(self, x: torch.Tensor, rows: torch.Tensor, targets: torch.Tensor):
         """Final RMSNorm of the gathered rows (lmi_rmsnorm_rows: the bits lmi_rmsnorm gives them) -> head GEMM into ONE reusable fp32 chunk of
         at most ``score_chunk_rows`` rows -> lmi_token_logprobs.  Peak extra memory: about one chunk, whatever the number of rows."""
@@ -1751,11 +1757,6 @@ class LeopardEngine:
                                       "the single-rank decode step; the tensor-parallel step has no captured form with it)")
         return int(logprobs)
 
-    @staticmethod
-    def _step_graph_name(st) -> str:
-        """Which captured step a state runs: greedy / sampled, each without and with the logprobs launch."""
-        return ("graph_s" if st.sampling else "graph") + ("" if st.logprobs is None else "_lp")
-
     def _set_logprobs(self, st, k: Optional[int]) -> None:
         st.logprobs = k
         if k is not None and st.lp_buf is None:                       # the rings: HIST slots beside a token history ring, else one
@@ -1765,7 +1766,8 @@ class LeopardEngine:
             st.lp, st.top_id = st.lp_buf[:n].view(torch.float32).view(ring, st.B), st.lp_buf[n:n * (1 + K)].view(ring, st.B, K)
             st.top_lp = st.lp_buf[n * (1 + K):].view(torch.float32).view(ring, st.B, K)
         if k is not None and st.lp_k != k:                            # top_k is a launch argument: the captured logprobs steps hold one value
-            st.graph_lp, st.graph_s_lp, st.lp_k = None, None, k
+            st.graphs.pop((False, True), None); st.graphs.pop((True, True), None)
+            st.lp_k = k
 
     def _rings_to_host(self, st):
         """(lp [ring, B], top_id [ring, B, 8], top_lp [ring, B, 8]) on the host: ONE copy of the state's ring buffer."""
@@ -1791,10 +1793,30 @@ class LeopardEngine:
         return lp[0].cpu(), ti[0].cpu(), tl[0].cpu()
 
     @staticmethod
-    def _generate_output(sequences, rows: Sequence[_LogprobRows], n_prompt: Sequence[int]) -> GenerateOutput:
-        seqs = sequences if isinstance(sequences, list) else [sequences]
-        res = [r.result(int(s.shape[-1]) - int(p)) for r, s, p in zip(rows, seqs, n_prompt)]
-        return GenerateOutput(sequences, [r[0] for r in res], [r[1] for r in res], [r[2] for r in res])
+    def _outputs(toks: Sequence[List[int]], like: Sequence[torch.Tensor], lpr: Optional[Sequence[_LogprobRows]], n_prompt: Sequence[int],
+                 one: bool = False):
+        """What a generation call returns for its requests: each token list as a LongTensor [1, n] on the device of the request's ids
+        (``like``) — the list of them, or (``one``) the tensor of the only request — and, with ``logprobs`` (``lpr``), the GenerateOutput
+        around that with the rows of the tokens after the n_prompt ids."""
+        seqs = [torch.tensor([t], dtype=torch.long, device=ids.device) for t, ids in zip(toks, like)]
+        seqs = seqs[0] if one else seqs
+        if lpr is None:
+            return seqs
+        res = [r.result(len(t) - int(p)) for r, t, p in zip(lpr, toks, n_prompt)]
+        return GenerateOutput(seqs, [r[0] for r in res], [r[1] for r in res], [r[2] for r in res])
+
+    def _first_tokens(self, logits: torch.Tensor, params: Optional[Sequence["SamplingParams"]], k: Optional[int]):
+        """The first token of each of n requests from its prefill / extend logits row ([n, >= vocab] or [vocab]): greedy (``params`` None) or
+        drawn with its SamplingParams at step 0, then — ``logprobs`` = k — one eager logprobs launch for all of them.  Returns (first
+        [n], the requests' _LogprobRows holding that first row, or None)."""
+        rows = logits.reshape(-1, logits.shape[-1])
+        first = [self.first_token(r) for r in rows] if params is None else self.sample_first(rows, params)
+        if k is None:
+            return first, None
+        lpr = [_LogprobRows(k) for _ in first]
+        for r, row in zip(lpr, zip(*self.first_logprobs(rows, first, k))):
+            r.add(*row)
+        return first, lpr
 
     def sample_first(self, logits: torch.Tensor, params: Sequence["SamplingParams"]) -> List[int]:
         """The first token of each request from its prefill logits row ([n, >= vocab] or [vocab]) through lmi_decode_sample at step 0
@@ -1812,44 +1834,57 @@ class LeopardEngine:
                                suppress=self.suppress_tokens)
         return [int(t) for t in tok.tolist()]
 
+    def _run_step(self, st, body, restore: tuple, capturable: bool = True) -> None:
+        """One decode step of ``st``.  ``body`` runs eagerly on the emulator, off a device, with graphs off or when the step is not
+        ``capturable``; otherwise the captured step of (st.sampling, with logprobs) is replayed — warmed up and captured on its first use
+        (two Python runs of ``body``), after each of which the device state the step advances (``restore``, and the logprob rings) is put back."""
+        if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs or not capturable:
+            body()
+            return
+        key = (st.sampling, st.logprobs is not None)
+        if key not in st.graphs:
+            st.graphs[key], _ = self._capture_graph(body, restore + (() if st.logprobs is None else (st.lp_buf,)))
+        st.graphs[key].replay()
+
     def _decode_run(self, st, cache: KVCache):
+        if st.layout != self.llm_packed:                                   # pack_llm_weights / unpack_llm_weights since the capture
+            st.graphs.clear()
+            st.layout = self.llm_packed
+        restore = (st.tok, st.pos, st.cu_k, st.step)
+        if self.tp_size == 1:
+            self._run_step(st, lambda: self._decode_body(st, cache), restore)
+            return
         # Tensor parallel: the step holds 2 all-reduces per layer.  Through RcclComm they are plain stream-ordered RCCL launches, which
         # HIP graph capture records like any kernel (RCCL supports capture; tests/test_gpu_dist.py captures and replays
         # lmi_allreduce on the device), so the step stays ONE graph replay per token; over a torch.distributed group (gloo in the
         # CPU tests, host-staged) it cannot be captured and runs eagerly.
         from .dist import RcclComm
-        if st.layout != self.llm_packed:                                   # pack_llm_weights / unpack_llm_weights since the capture
-            st.graph, st.graph_s, st.graph_lp, st.graph_s_lp, st.layout = None, None, None, None, self.llm_packed
-        gname = self._step_graph_name(st)                                  # greedy and sampled steps, without / with logprobs: one captured graph each
-        tp_capturable = self.tp_size == 1 or (isinstance(self.comm, RcclComm) and self.tp_decode_graph)
-        if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs or not tp_capturable or st.graph_failed:
+        comm = self.comm
+        capturable = isinstance(comm, RcclComm) and self.tp_decode_graph and not st.graph_failed
+        sent, keep = [], []                # comm.sent_bytes before each Python run of the body: none = a replay, two = warm-up, then capture
+
+        def body():
+            if capturable and not sent:
+                keep.extend(t.clone() for t in restore)
+            sent.append(comm.sent_bytes)
+            self._decode_body(st, cache)
+        try:
+            self._run_step(st, body, restore, capturable)
+        except Exception as exc:           # a communicator that cannot be captured: run the step eagerly from now on
+            if len(sent) < 2:              # (not the capture: the warm-up or an eager step failed)
+                raise
+            import warnings
+            warnings.warn(f"tensor-parallel decode step could not be captured in a HIP graph ({exc}); running it eagerly")
+            st.graph_failed = True
+            torch.cuda.synchronize(self.device)
+            for t, v in zip(restore, keep):
+                t.copy_(v)
             self._decode_body(st, cache)
             return
-        if getattr(st, gname) is None:
-            restore = (st.tok, st.pos, st.cu_k, st.step) + (() if st.logprobs is None else (st.lp_buf,))
-            body = lambda: self._decode_body(st, cache)
-            keep = self._warm_up(body, restore)        # (what the warm-up sends counts in comm.sent_bytes)
-            sent0 = self.comm.sent_bytes if self.comm is not None else 0
-            try:
-                g, _ = self._capture(body, restore, keep)
-            except Exception as exc:                   # a communicator that cannot be captured: run the step eagerly from now on
-                if self.tp_size == 1:
-                    raise
-                import warnings
-                warnings.warn(f"tensor-parallel decode step could not be captured in a HIP graph ({exc}); running it eagerly")
-                st.graph_failed = True
-                torch.cuda.synchronize(self.device)
-                for t, v in zip(restore, keep):
-                    t.copy_(v)
-                self._decode_body(st, cache)
-                return
-            st.graph_comm_bytes = (self.comm.sent_bytes - sent0) if self.comm is not None else 0    # what one replay puts on the links
-            if self.comm is not None:
-                self.comm.sent_bytes = sent0           # capture records, it does not send
-            setattr(st, gname, g)
-        getattr(st, gname).replay()
-        if self.comm is not None:
-            self.comm.sent_bytes += st.graph_comm_bytes
+        if len(sent) == 2:                 # captured now: what the capture counted is what one replay puts on the links — the replay that followed
+            st.graph_comm_bytes = comm.sent_bytes - sent[1]
+        elif not sent:
+            comm.sent_bytes += st.graph_comm_bytes
 
     def _decode_seed(self, st, cache: KVCache, token_id: int):
         if cache.length >= cache.capacity:
@@ -1910,6 +1945,17 @@ class LeopardEngine:
                 lpr.add(lp[0], ti[0], tl[0])
         return out
 
+    def _continue_single(self, prompt: List[int], first: int, pieces, max_new_tokens: int, eos, sampling: Optional[SamplingParams],
+                         lpr: Optional[_LogprobRows]) -> List[int]:
+        """One request whose K / V rows are ``pieces`` (_load_rows) continued on the engine's ONE generation cache and its captured batch-1
+        step: a chunk of one suffix, or the requests of a call one after another where the shape has no batched decode (toy configurations
+        the skinny-M kernels do not cover)."""
+        S = sum(n for _, _, n in pieces)
+        cache = self._generation_cache(S + max_new_tokens)
+        self._load_rows(pieces, cache.k, cache.v, 0)
+        cache.length = S
+        return self._greedy_loop(prompt, first, cache, max_new_tokens, eos, sampling, lpr)
+
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, tiles: Optional[torch.Tensor], max_new_tokens: int = 128,
                  eos_token_id: Sequence[int] = (128001, 128009), sampling: Optional[SamplingParams] = None,
@@ -1922,15 +1968,10 @@ class LeopardEngine:
         S = self.merged_len(ids)
         cache = self._generation_cache((self.tp_padded_len(S) if self.tp_size > 1 else S) + max_new_tokens)
         res = self.prefill(ids, tiles, cache=cache)
-        first = self.first_token(res.logits_last) if sampling is None else self.sample_first(res.logits_last, [sampling])[0]
-        lpr = None
-        if k is not None:
-            lpr = _LogprobRows(k)
-            lpr.add(*self.first_logprobs(res.logits_last, [first], k))
-        out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], first, cache, max_new_tokens,
-                                set(int(e) for e in eos_token_id), sampling, lpr)
-        seq = torch.tensor([out], dtype=torch.long, device=input_ids.device)
-        return seq if k is None else self._generate_output(seq, [lpr], [ids.numel()])
+        first, lpr = self._first_tokens(res.logits_last, None if sampling is None else [sampling], k)
+        out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], first[0], cache, max_new_tokens,
+                                set(int(e) for e in eos_token_id), sampling, lpr and lpr[0])
+        return self._outputs([out], [input_ids], lpr, [ids.numel()], one=True)
 
     # ------------------------------------------------------------------------------------------------
     # f4: batched decode.  B sequences advance together: ONE pass over the weights per step serves B tokens (lmi_gemm_skinny),
@@ -1948,21 +1989,28 @@ class LeopardEngine:
         return (hd == 128 and D % 128 == 0 and W.llm_ff % 128 == 0 and (2 * W.llm_ff) % 64 == 0 and ((H + 2 * KV) * hd) % 16 == 0 and
                 W.lm_head.shape[0] % 16 == 0 and D % 16 == 0)
 
+    def _pooled_state(self, key, fits, build) -> DecodeState:
+        """The pooled decode state kept under ``key``: reused when it ``fits`` and belongs to the current precision mode, else built anew
+        (``build``).  Bounded: a serving process that sees many batch sizes keeps the pools of the two most recent ones (each is B x capacity
+        KV rows)."""
+        states = self._batch_states
+        st = states.get(key)
+        if st is not None and fits(st) and st.mode == (self.precision, self.decode_precision):
+            return st
+        st = build()
+        while len(states) >= 2:
+            states.pop(next(iter(states)))
+        states[key] = st
+        return st
+
     def _batch_state(self, B: int, need: int) -> DecodeState:
         """Static buffers + pooled KV cache + captured graph of a B-sequence decode step (kept per engine and reused: the graph reads
         positions / key counts from device memory and its launch geometry depends on (B, capacity) only)."""
-        states = self._batch_states
-        st = states.get(B)
-        if st is not None and st.capacity >= need and st.mode == (self.precision, self.decode_precision):
+        def build():
+            st = self._decode_buffers(B, (need + 1023) // 1024 * 1024)
+            self._pool_buffers(st)
             return st
-        cap = (need + 1023) // 1024 * 1024
-        st = self._decode_buffers(B, cap)
-        self._pool_buffers(st)
-        # bounded: a serving process that sees many batch sizes keeps the pools of the two most recent ones (each is B x capacity KV rows)
-        while len(states) >= 2:
-            states.pop(next(iter(states)))
-        states[B] = st
-        return st
+        return self._pooled_state(B, lambda st: st.capacity >= need, build)
 
     SHARED_OWN_ROWS = 256              # shared-prefix decode: a slot's own rows (question + new tokens) are rounded up to this ...
     SHARED_PREFIX_ROWS = 1024          # ... and the one prefix copy to this, so that calls of about the same shape reuse one captured step
@@ -1987,27 +2035,21 @@ class LeopardEngine:
         tokens) + one prefix buffer of prefix_capacity rows per layer.  Kept per (B, own capacity, prefix capacity) next to the copy states,
         under the same bound of two retained pools; a later call whose own rows and prefix fit reuses the buffers and the captured step
         (the prefix length is a device int)."""
-        states = self._batch_states
-        key = ("shared", B)
-        st = states.get(key)
-        if (st is not None and st.capacity >= need_own and st.prefix_capacity >= need_prefix and st.mode == (self.precision, self.decode_precision)):
+        def build():
+            tc, dev = self.cfg.text_config, self.device
+            KV, hd = self._llm_heads()[1], tc.head_dim
+            own = (need_own + self.SHARED_OWN_ROWS - 1) // self.SHARED_OWN_ROWS * self.SHARED_OWN_ROWS
+            pcap = (need_prefix + self.SHARED_PREFIX_ROWS - 1) // self.SHARED_PREFIX_ROWS * self.SHARED_PREFIX_ROWS
+            self._batch_states.pop(("shared", B), None)                # the pool it replaces goes first: never two of one batch size
+            st = self._decode_buffers(B, own, prefix_capacity=pcap)
+            self._pool_buffers(st)
+            n_layers = len(self.W.llm_layers)
+            st.kp = [torch.zeros(pcap, KV * hd, dtype=self.dtype, device=dev) for _ in range(n_layers)]
+            st.vp = [torch.zeros(pcap, KV * hd, dtype=self.dtype, device=dev) for _ in range(n_layers)]
+            st.prefix_capacity = pcap
+            st.prefix_len = torch.ones(1, dtype=torch.int32, device=dev)
             return st
-        tc, dev = self.cfg.text_config, self.device
-        KV, hd = self._llm_heads()[1], tc.head_dim
-        own = (need_own + self.SHARED_OWN_ROWS - 1) // self.SHARED_OWN_ROWS * self.SHARED_OWN_ROWS
-        pcap = (need_prefix + self.SHARED_PREFIX_ROWS - 1) // self.SHARED_PREFIX_ROWS * self.SHARED_PREFIX_ROWS
-        states.pop(key, None)                                          # the pool it replaces goes first: never two of one batch size
-        st = self._decode_buffers(B, own, prefix_capacity=pcap)
-        self._pool_buffers(st)
-        n_layers = len(self.W.llm_layers)
-        st.kp = [torch.zeros(pcap, KV * hd, dtype=self.dtype, device=dev) for _ in range(n_layers)]
-        st.vp = [torch.zeros(pcap, KV * hd, dtype=self.dtype, device=dev) for _ in range(n_layers)]
-        st.prefix_capacity = pcap
-        st.prefix_len = torch.ones(1, dtype=torch.int32, device=dev)
-        while len(states) >= 2:
-            states.pop(next(iter(states)))
-        states[key] = st
-        return st
+        return self._pooled_state(("shared", B), lambda st: st.capacity >= need_own and st.prefix_capacity >= need_prefix, build)
 
     def _pool_buffers(self, st: DecodeState) -> None:
         """The pooled KV slots and the device side of continuous batching of a B-sequence decode state."""
@@ -2125,16 +2167,7 @@ class LeopardEngine:
         self._choose(st, st.logits, k_len=st.k_len, live=st.live, budget=st.budget, eos=st.eos, hist=st.hist, hist_pos=st.hist_pos)
 
     def _batch_decode_run(self, st):
-        if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs:
-            self._batch_decode_body(st)
-            return
-        gname = self._step_graph_name(st)                                  # greedy and sampled steps, without / with logprobs: one captured graph each
-        if getattr(st, gname) is None:
-            g, _ = self._capture_graph(lambda: self._batch_decode_body(st),
-                                       (st.tok, st.pos, st.k_len, st.live, st.budget, st.hist, st.hist_pos, st.step) +
-                                       (() if st.logprobs is None else (st.lp_buf,)))
-            setattr(st, gname, g)
-        getattr(st, gname).replay()
+        self._run_step(st, lambda: self._batch_decode_body(st), (st.tok, st.pos, st.k_len, st.live, st.budget, st.hist, st.hist_pos, st.step))
 
     def _greedy_loop_batch(self, st, prompts: List[List[int]], first: List[int], seq_lens: List[int], max_new_tokens: int, eos,
                            sampling: Optional[Sequence[SamplingParams]] = None, own_lens: Optional[List[int]] = None,
@@ -2224,7 +2257,7 @@ class LeopardEngine:
         st.live.zero_(); st.budget.zero_(); st.pos.zero_(); st.k_len.fill_(1); st.tok.zero_(); st.hist_pos.zero_()
         st.sampling = sampling is not None
         self._set_logprobs(st, k)
-        lpr = None if k is None else [_LogprobRows(k) for _ in samples]
+        lpr = None if k is None else [None] * len(samples)          # a request's rows start with its first token's (admit)
         eos_set = set(eos)
         outs: List[Optional[List[int]]] = [None] * len(samples)
         slot_sample = [-1] * B                                       # which sample a slot runs (-1: free)
@@ -2246,11 +2279,10 @@ class LeopardEngine:
                     scratch = self._stream_cache = KVCache(self.cfg, (S + 1023) // 1024 * 1024, self.dtype, self.device)
                 scratch.length = 0
                 res = self.prefill(ids.reshape(1, -1), tiles, cache=scratch)
-                first = self.first_token(res.logits_last) if sampling is None else self.sample_first(res.logits_last, [req(i)])[0]
-                out = [int(t) for t in ids.reshape(-1).tolist()] + [first]
-                outs[i] = out
+                (first,), rows = self._first_tokens(res.logits_last, None if sampling is None else [req(i)], k)
+                outs[i] = [int(t) for t in ids.reshape(-1).tolist()] + [first]
                 if lpr is not None:
-                    lpr[i].add(*self.first_logprobs(res.logits_last, [first], k))
+                    lpr[i] = rows[0]
                 if first in eos_set or max_new_tokens <= 1:
                     continue                                          # finished by the prefill alone
                 self._move_kv(scratch, 0, S, st.k, st.v, j * st.capacity)
@@ -2296,8 +2328,7 @@ class LeopardEngine:
                     admit(j)
         if stats is not None:
             stats.update(steps=n_steps, slot_steps=slot_steps, live_slot_steps=live_steps, batch_size=B)
-        seqs = [torch.tensor([o], dtype=torch.long, device=samples[i][0].device) for i, o in enumerate(outs)]
-        return seqs if k is None else self._generate_output(seqs, lpr, [ids.numel() for ids, _ in samples])
+        return self._outputs(outs, [ids for ids, _ in samples], lpr, [ids.numel() for ids, _ in samples])
 
     @torch.no_grad()
     def generate_batch(self, samples: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], max_new_tokens: int = 128,
@@ -2327,43 +2358,21 @@ class LeopardEngine:
         x, seq_lens = self._pack_requests(samples)
         packed = KVCache(self.cfg, sum(seq_lens), self.dtype, self.device)
         last, _ = self.llm_prefill(x, seq_lens, cache=packed)
-        if sampling is None:
-            first = [self.first_token(last[j]) for j in range(last.shape[0])]
-        else:
-            first = self.sample_first(last, [req(j) for j in range(last.shape[0])])
-        lpr = None
-        if k is not None:
-            lpr = [_LogprobRows(k) for _ in samples]
-            f_lp, f_ti, f_tl = self.first_logprobs(last, first, k)
-            for j in range(len(samples)):
-                lpr[j].add(f_lp[j], f_ti[j], f_tl[j])
-        n_prompt = [ids.numel() for ids, _ in samples]
-        eos = set(int(e) for e in eos_token_id)
-        if not self._batch_decode_supported():
-            # shapes the skinny-M kernels do not cover (toy configurations): the samples continue one after another on the engine's ONE
-            # generation cache and its captured batch-1 step
-            outs, off = [], 0
-            for j, ((ids, _), S, nxt) in enumerate(zip(samples, seq_lens, first)):
-                cache = self._generation_cache(S + max_new_tokens)
-                self._move_kv(packed, off, S, cache.k, cache.v, 0)
-                cache.length = S
-                off += S
-                out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], nxt, cache, max_new_tokens, eos, req(j),
-                                        None if lpr is None else lpr[j])
-                outs.append(torch.tensor([out], dtype=torch.long, device=ids.device))
-            return outs if k is None else self._generate_output(outs, lpr, n_prompt)
-        st = self._batch_state(len(samples), max(seq_lens) + max_new_tokens)
-        off = 0
-        for j, S in enumerate(seq_lens):
-            self._move_kv(packed, off, S, st.k, st.v, j * st.capacity)
-            off += S
-        del packed
+        first, lpr = self._first_tokens(last, None if sampling is None else [req(j) for j in range(last.shape[0])], k)
         prompts = [[int(t) for t in ids.reshape(-1).tolist()] for ids, _ in samples]
-        outs = self._greedy_loop_batch(st, prompts, first, seq_lens, max_new_tokens, eos,
-                                       None if sampling is None else [req(j) for j in range(len(samples))], lpr=lpr)
-        seqs = [torch.tensor([o], dtype=torch.long, device=ids.device) for o, (ids, _) in zip(outs, samples)]
-        return seqs if k is None else self._generate_output(seqs, lpr, n_prompt)
-
+        eos = set(int(e) for e in eos_token_id)
+        offs = [0] + [int(c) for c in np.cumsum(seq_lens)]
+        if not self._batch_decode_supported():
+            outs = [self._continue_single(prompts[j], first[j], [(packed, offs[j], S)], max_new_tokens, eos, req(j), lpr and lpr[j])
+                    for j, S in enumerate(seq_lens)]
+        else:
+            st = self._batch_state(len(samples), max(seq_lens) + max_new_tokens)
+            for j, S in enumerate(seq_lens):
+                self._load_rows([(packed, offs[j], S)], st.k, st.v, j * st.capacity)
+            del packed
+            outs = self._greedy_loop_batch(st, prompts, first, seq_lens, max_new_tokens, eos,
+                                           None if sampling is None else [req(j) for j in range(len(samples))], lpr=lpr)
+        return self._outputs(outs, [ids for ids, _ in samples], lpr, [len(p) for p in prompts])
 
     # ------------------------------------------------------------------------------------------------
     # Continuing from a cached prefix: N new row ranges against rows that are already in a KV cache.  ``extend`` fans one read-only prefix
@@ -2682,8 +2691,8 @@ class LeopardEngine:
             raise ValueError(f"generate_shared: the prefix cache holds {prefix.length} rows, prefix_ids merge to {P}")
         eos = set(int(e) for e in eos_token_id)
         head = [int(t) for t in pids.reshape(-1).tolist()]
-        outs: List[torch.Tensor] = []
-        rows_all: List[_LogprobRows] = []
+        toks: List[List[int]] = []
+        rows_all: Optional[List[_LogprobRows]] = None if k is None else []
         for c0 in range(0, len(sfx), self.MAX_DECODE_BATCH):
             chunk = sfx[c0:c0 + self.MAX_DECODE_BATCH]
             req = [None if sampling is None else sampling.for_request(c0 + j) for j in range(len(chunk))]
@@ -2691,43 +2700,27 @@ class LeopardEngine:
             stepping = max_new_tokens > 1
             kv = KVCache(self.cfg, sum(lens), self.dtype, self.device) if stepping else None
             res = self.extend(prefix, chunk, kv_out=kv)
-            if sampling is None:
-                first = [self.first_token(res.logits[j]) for j in range(len(chunk))]
-            else:
-                first = self.sample_first(res.logits, req)
-            lpr = None
-            if k is not None:
-                lpr = [_LogprobRows(k) for _ in chunk]
-                f_lp, f_ti, f_tl = self.first_logprobs(res.logits, first, k)
-                for j in range(len(chunk)):
-                    lpr[j].add(f_lp[j], f_ti[j], f_tl[j])
+            first, lpr = self._first_tokens(res.logits, None if sampling is None else req, k)
+            if lpr is not None:
                 rows_all += lpr
             prompts = [head + [int(t) for t in ids.reshape(-1).tolist()] for ids in chunk]
             offs = [0] + [int(c) for c in np.cumsum(lens)]
+            own = [[(kv, offs[j], s)] for j, s in enumerate(lens)]       # a request's own rows ...
+            whole = [[(prefix, 0, P)] + o for o in own]                  # ... and all of them: the prefix rows first
             if not stepping:
-                toks = [p + [f] for p, f in zip(prompts, first)] if max_new_tokens == 1 else prompts
+                toks += [p + [f] for p, f in zip(prompts, first)] if max_new_tokens == 1 else prompts
             elif len(chunk) == 1 or not self._batch_decode_supported():
-                toks = []
-                for j, s in enumerate(lens):
-                    cache = self._generation_cache(P + s + max_new_tokens)
-                    self._move_kv(prefix, 0, P, cache.k, cache.v, 0)
-                    self._move_kv(kv, offs[j], s, cache.k, cache.v, P)
-                    cache.length = P + s
-                    toks.append(self._greedy_loop(prompts[j], first[j], cache, max_new_tokens, eos, req[j], None if lpr is None else lpr[j]))
-            elif decode == "shared":
-                st = self._shared_state(len(chunk), max(lens) + max_new_tokens, P)
-                self._move_kv(prefix, 0, P, st.kp, st.vp, 0)           # the one prefix copy (the captured step reads state-owned memory only)
-                st.prefix_len.fill_(P)
-                for j, s in enumerate(lens):
-                    self._move_kv(kv, offs[j], s, st.k, st.v, j * st.capacity)
-                toks = self._greedy_loop_batch(st, prompts, first, [P + s for s in lens], max_new_tokens, eos,
-                                               None if sampling is None else req, own_lens=lens, lpr=lpr)
+                toks += [self._continue_single(prompts[j], first[j], whole[j], max_new_tokens, eos, req[j], lpr and lpr[j])
+                         for j in range(len(chunk))]
             else:
-                st = self._batch_state(len(chunk), P + max(lens) + max_new_tokens)
-                for j, s in enumerate(lens):
-                    self._move_kv(prefix, 0, P, st.k, st.v, j * st.capacity)
-                    self._move_kv(kv, offs[j], s, st.k, st.v, j * st.capacity + P)
-                toks = self._greedy_loop_batch(st, prompts, first, [P + s for s in lens], max_new_tokens, eos,
-                                               None if sampling is None else req, lpr=lpr)
-            outs += [torch.tensor([o], dtype=torch.long, device=ids.device) for o, ids in zip(toks, chunk)]
-        return outs if k is None else self._generate_output(outs, rows_all, [len(head) + int(t.numel()) for t in sfx])
+                if decode == "shared":
+                    st = self._shared_state(len(chunk), max(lens) + max_new_tokens, P)
+                    self._load_rows([(prefix, 0, P)], st.kp, st.vp, 0)   # the one prefix copy (the captured step reads state-owned memory only)
+                    st.prefix_len.fill_(P)
+                else:
+                    st = self._batch_state(len(chunk), P + max(lens) + max_new_tokens)
+                for j in range(len(chunk)):
+                    self._load_rows(own[j] if decode == "shared" else whole[j], st.k, st.v, j * st.capacity)
+                toks += self._greedy_loop_batch(st, prompts, first, [P + s for s in lens], max_new_tokens, eos, None if sampling is None else req,
+                                                own_lens=lens if decode == "shared" else None, lpr=lpr)
+        return self._outputs(toks, sfx, rows_all, [len(head) + int(t.numel()) for t in sfx])

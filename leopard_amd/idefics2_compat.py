@@ -28,7 +28,6 @@ import torch
 
 from .checkpoint import CheckpointSource
 from .config import Idefics2Config, PerceiverConfig, TextConfig, VisionConfig
-from .engine import KVCache, _LogprobRows
 from .idefics2 import Idefics2Engine, Idefics2Weights, preprocess_image_u8
 from .ops import Ops
 from . import sampling
@@ -281,18 +280,12 @@ class Idefics2ForConditionalGeneration:
             raise NotImplementedError("batch 1 per call, as in the reference script (IDEF:88-97)")
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             raise NotImplementedError("padded prompts are not produced by the reference script (batch 1)")
-        eng = self.engine
         images = None if pixel_values is None else self.unpad_images(pixel_values, pixel_attention_mask, self.patch_validity,
                                                                      self.config.vision_config.patch_size)
         eos = self.eos_token_id if eos_token_id is None else (tuple(eos_token_id) if isinstance(eos_token_id, (list, tuple)) else (int(eos_token_id),))
-        ids = input_ids.reshape(1, -1)
-        cache = eng._generation_cache(ids.shape[1] + max_new_tokens)           # one cache + captured decode graph per engine
-        res = eng.prefill(ids.to(self.device), images, cache=cache)
-        first = eng.first_token(res.logits_last) if sp is None else eng.sample_first(res.logits_last, [sp])[0]
-        lpr = None
-        if k is not None:
-            lpr = _LogprobRows(k)
-            lpr.add(*eng.first_logprobs(res.logits_last, [first], k))
-        out = eng._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], first, cache, max_new_tokens, set(int(e) for e in eos), sp, lpr)
-        seq = torch.tensor([out], dtype=torch.long, device=input_ids.device)
-        return seq if k is None else sampling.logprob_outputs(eng._generate_output(seq, [lpr], [ids.numel()]))[0]
+        out = self.engine.generate(input_ids.reshape(1, -1).to(self.device), images, max_new_tokens=max_new_tokens, eos_token_id=eos,
+                                   sampling=sp, logprobs=k)            # one cache + captured decode graph per engine (_generation_cache)
+        if k is None:
+            return out.to(input_ids.device)
+        out.sequences = out.sequences.to(input_ids.device)
+        return sampling.logprob_outputs(out)[0]

@@ -172,7 +172,7 @@ def test_generate_batch_lo4_runs_the_captured_step_on_pairs(lo4_engine, B):
         eng._batch_decode_body = body
     st = eng._batch_states[B]
     assert st.hl == (B <= 8)
-    assert steps == [(B, B <= 8)] * 2 and st.graph is not None          # warm-up + capture: afterwards the graph replays (no Python body)
+    assert steps == [(B, B <= 8)] * 2 and st.graphs.get((False, False)) is not None          # warm-up + capture: afterwards the graph replays (no Python body)
     for (ids, tiles), one, got in zip(samples, singles, batch):
         S_in = ids.shape[1]
         assert got.shape == one.shape and int(got[0, S_in]) == int(one[0, S_in])

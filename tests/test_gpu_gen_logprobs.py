@@ -220,6 +220,39 @@ def test_generated_logprobs_agree_with_score(mid, ops):
     assert (gap <= bound).all(), (gap, bound)
 
 
+def test_a_different_k_captures_the_logprobs_step_again(mid, monkeypatch):
+    """The captured steps of one decode state across calls: the same k replays the logprobs step it captured (the Python body ran twice in
+    all, warm-up and capture); a different k — top_k is a launch argument — captures a new one and leaves the greedy step's graph alone; a
+    greedy call in between replays that old graph."""
+    cfg, eng = mid.config, mid.engine
+    ids = text_requests(cfg, 1, seed=7)[0][0]
+    gen = lambda k: eng.generate(ids, None, max_new_tokens=4, eos_token_id=(), logprobs=k)
+    plain = gen(None)
+    gen(1)                                                              # whatever k the earlier tests left behind: now it is 1
+    st = eng._gen_cache._decode_state
+    greedy = st.graphs[(False, False)]
+    assert greedy is not None and st.lp_k == 1
+    bodies = []
+    real = eng._decode_body
+    monkeypatch.setattr(eng, "_decode_body", lambda s, cache: (bodies.append(s.logprobs), real(s, cache))[1])
+    two = gen(2)
+    g2 = st.graphs[(False, True)]
+    assert g2 is not None and bodies == [2, 2]                          # warm-up + capture; the other steps are replays
+    again = gen(2)
+    assert st.graphs[(False, True)] is g2 and bodies == [2, 2]          # same k: the same object, no Python body
+    assert torch.equal(gen(None), plain) and st.graphs[(False, False)] is greedy and st.graphs[(False, True)] is g2 and bodies == [2, 2]
+    three = gen(3)
+    g3 = st.graphs[(False, True)]
+    assert g3 is not None and g3 is not g2 and bodies == [2, 2, 3, 3] and st.lp_k == 3
+    assert st.graphs[(False, False)] is greedy                          # the greedy step was not captured again ...
+    assert torch.equal(gen(None), plain) and bodies == [2, 2, 3, 3]     # ... and still replays
+    assert eng._gen_cache._decode_state is st
+    for out, k in ((two, 2), (again, 2), (three, 3)):
+        assert torch.equal(out.sequences, plain) and out.top_ids[0].shape == (4, k)
+    assert torch.equal(two.token_logprobs[0], again.token_logprobs[0]) and torch.equal(two.token_logprobs[0], three.token_logprobs[0])
+    assert torch.equal(three.top_ids[0][:, :2], two.top_ids[0])
+
+
 def test_idefics2_surface(ops):
     """Idefics2 (sliding window, a suppress_tokens list): tokens as without logprobs; a suppressed id is never generated."""
     from leopard_amd import idefics2_compat as IC, sampling

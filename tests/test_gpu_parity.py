@@ -553,7 +553,7 @@ def test_generate_batch_decodes_together_and_equals_per_sample_generate(ops):
     eng._batch_decode_body = body
     assert set(steps) == {4} and len(steps) == 2                       # warm-up + capture: afterwards the graph replays (no Python body)
     st = eng._batch_states[4]
-    assert st.graph is not None
+    assert st.graphs.get((False, False)) is not None
     for (ids, tiles), one, got in zip(samples, singles, batch):
         S_in = ids.shape[1]
         assert got.shape == one.shape and int(got[0, S_in]) == int(one[0, S_in])
@@ -603,7 +603,7 @@ def test_generate_stream_continuous_batching_on_device(ops):
     stats = {}
     got = eng.generate_stream(samples, batch_size=4, max_new_tokens=T, eos_token_id=eos, stats=stats)
     eng._batch_decode_body = body
-    assert len(bodies) == 2 and eng._batch_states[4].graph is not None            # warm-up + capture; every step afterwards is a replay
+    assert len(bodies) == 2 and eng._batch_states[4].graphs.get((False, False)) is not None            # warm-up + capture; every step afterwards is a replay
     n_diff = 0
     for (ids, tiles), one, out in zip(samples, singles, got):
         S_in = ids.shape[1]

@@ -115,17 +115,17 @@ def test_parameters_change_without_a_recapture(model):
     eng = model.engine
     model.generate(ids, max_new_tokens=4, do_sample=True, temperature=0.7, seed=1)
     st = eng._gen_cache._decode_state
-    g_s, g = st.graph_s, st.graph
+    g_s, g = st.graphs.get((True, False)), st.graphs.get((False, False))
     assert g_s is not None
     for kw in (dict(temperature=1.5), dict(top_k=3), dict(top_p=0.5), dict(temperature=0.3, top_k=0, top_p=0.9)):
         model.generate(ids, max_new_tokens=4, do_sample=True, seed=2, **kw)
-        assert eng._gen_cache._decode_state is st and st.graph_s is g_s and st.graph is g
+        assert eng._gen_cache._decode_state is st and st.graphs.get((True, False)) is g_s and st.graphs.get((False, False)) is g
     reqs = [(p, None) for p in _prompts(4, seed=8)]
     model.generate_stream(reqs, batch_size=4, max_new_tokens=5, seed=3, do_sample=True, temperature=0.8)
     bst = eng._batch_states[4]
-    bg = bst.graph_s
+    bg = bst.graphs.get((True, False))
     model.generate_stream(reqs, batch_size=4, max_new_tokens=5, seed=3, do_sample=True, temperature=2.0, top_k=7, top_p=0.6)
-    assert eng._batch_states[4] is bst and bst.graph_s is bg
+    assert eng._batch_states[4] is bst and bst.graphs.get((True, False)) is bg
 
 
 def test_stream_tokens_do_not_depend_on_batch_size(model):

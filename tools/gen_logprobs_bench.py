@@ -65,17 +65,18 @@ def step_times(B):
         run = lambda: eng._batch_decode_run(st)  # noqa: E731
     res = {a: [] for a in ARMS}
     graphs = {}                                                               # logprobs=0 and logprobs=8 are two captures of the same two graph slots
+    slot = lambda: (st.sampling, True)  # noqa: E731  (DecodeState.graphs)
     for r in range(args.rounds + 1):
         for arm, (sampled, k) in ARMS.items():
             st.sampling = sampled
             eng._set_logprobs(st, k)                                          # (allocates the rings on first use; a new k drops the captured pair)
-            if k is not None:
-                st.graph_lp = graphs.get(arm)
+            if arm in graphs:
+                st.graphs[slot()] = graphs[arm]
             if B > 1:
                 st.hist_pos.zero_()
             run()                                                             # (captures on first use)
             if k is not None:
-                graphs[arm] = st.graph_lp
+                graphs[arm] = st.graphs[slot()]
             t = timed(run, args.steps)
             if r > 0:                                                         # round 0: capture + warm-up
                 res[arm].append(t)

@@ -188,9 +188,8 @@ def scenarios(ops):
             eng.generate_shared(ids3[:, :4], tiles(3, 2), sfx, max_new_tokens=3, eos_token_id=())
         return run
 
-    def idefics2(mode):
+    def idefics2_micro():
         from leopard_amd.config import Idefics2Config, PerceiverConfig
-        from leopard_amd.idefics2 import Idefics2Engine, Idefics2SynthSource, Idefics2Weights
         cfg = Idefics2Config(
             vision_config=VisionConfig(hidden_size=1152, intermediate_size=100, num_hidden_layers=1, num_attention_heads=16,
                                        image_size=56, patch_size=14),
@@ -198,12 +197,17 @@ def scenarios(ops):
                                    num_key_value_heads=1, vocab_size=256, rope_theta=10000.0, rope_scaling=None, sliding_window=6),
             perceiver_config=PerceiverConfig(n_latents=3, depth=2, n_heads=1, head_dim=96, num_key_value_heads=1),
             image_token_id=250, longest_edge=56)
-        eng = Idefics2Engine(cfg, Idefics2Weights.build(cfg, Idefics2SynthSource(cfg, ops, "cpu", torch.float16), torch.float16), ops=ops,
-                             device="cpu")
-        eng.precision = mode
         rng = np.random.default_rng(8)
         images = [torch.from_numpy(rng.standard_normal(s).astype(np.float32)) for s in ((3, 42, 56), (3, 58, 30))]
         ids = torch.tensor([[5, 7] + [250] * 3 + [9, 11, 13] + [250] * 3 + [17, 19]])
+        return cfg, images, ids
+
+    def idefics2(mode):
+        from leopard_amd.idefics2 import Idefics2Engine, Idefics2SynthSource, Idefics2Weights
+        cfg, images, ids = idefics2_micro()
+        eng = Idefics2Engine(cfg, Idefics2Weights.build(cfg, Idefics2SynthSource(cfg, ops, "cpu", torch.float16), torch.float16), ops=ops,
+                             device="cpu")
+        eng.precision = mode
         return lambda: eng.prefill(ids, images)
 
     def tensor_parallel(mode):
@@ -219,6 +223,76 @@ def scenarios(ops):
         out[f"extend_append_shared_{mode}"] = continuation(mode)
         out[f"idefics2_prefill_{mode}"] = idefics2(mode)
         out[f"tp_prefill_{mode}"] = tensor_parallel(mode)
+
+    # the generation paths a fold of the first-token rule, the step runner, the slot filler and the output assembly rewrites: logprobs on
+    # every entry point, a ring drain inside generate_batch, its chunking, the sequential fallback of shapes without a batched decode, every
+    # arm of generate_shared and generate through the Idefics2 surface class
+    def gen_logprobs(kind, sampling, k):
+        eng = engine(ops)
+        if kind == "generate":
+            return lambda: eng.generate(long_ids[:, :6], tiles(4, 1), max_new_tokens=4, eos_token_id=(), sampling=sampling, logprobs=k)
+        if kind == "generate_batch":                  # 10 steps: the rings drain after step 8 (HIST) and again at the end
+            return lambda: eng.generate_batch(samples, max_new_tokens=11, eos_token_id=(), sampling=sampling, logprobs=k)
+        return lambda: eng.generate_stream(samples + text_only, batch_size=2, max_new_tokens=11, eos_token_id=(), sampling=sampling, logprobs=k)
+    out["generate_greedy_logprobs0"] = gen_logprobs("generate", None, 0)
+    out["generate_sampled_logprobs3"] = gen_logprobs("generate", sp, 3)
+    out["generate_batch_sampled_logprobs3_two_drains"] = gen_logprobs("generate_batch", sp, 3)
+    out["generate_stream_greedy_logprobs2"] = gen_logprobs("generate_stream", None, 2)
+    out["generate_stream_sampled_logprobs2"] = gen_logprobs("generate_stream", sp, 2)
+
+    def gen_batch_chunks():                           # a chunk of MAX_DECODE_BATCH requests + the single-request arm
+        eng = engine(ops)
+        g = np.random.default_rng(4)
+        reqs = [(torch.tensor([[int(v) for v in g.integers(0, 240, 3 + j % 4)]]), None) for j in range(17)]
+        return lambda: eng.generate_batch(reqs, max_new_tokens=2, eos_token_id=(), logprobs=1)
+    out["generate_batch_17_requests_logprobs1"] = gen_batch_chunks()
+
+    sfx2 = [torch.tensor([[7, 8, 9]]), torch.tensor([[11, 12, 13, 14, 15]])]
+
+    def sequential_fallback():
+        eng = engine(ops)
+        eng._batch_decode_supported = lambda: False
+        return lambda: (eng.generate_batch(samples, max_new_tokens=11, eos_token_id=(), sampling=sp, logprobs=3),
+                        eng.generate_shared(ids3[:, :4], tiles(3, 2), sfx2, max_new_tokens=3, eos_token_id=(), logprobs=0))
+    out["sequential_fallback_batch_and_shared"] = sequential_fallback()
+
+    def shared_copy():
+        eng = engine(ops)
+        return lambda: eng.generate_shared(ids3[:, :4], tiles(3, 2), sfx2, max_new_tokens=11, eos_token_id=(), sampling=sp, decode="copy",
+                                           logprobs=2)
+    out["generate_shared_copy_sampled_logprobs2"] = shared_copy()
+
+    def shared_small():                               # one suffix: the batch-1 arm; max_new_tokens=1: no stepping
+        eng = engine(ops)
+        return lambda: (eng.generate_shared(ids3[:, :4], tiles(3, 2), sfx2[:1], max_new_tokens=3, eos_token_id=(), logprobs=1),
+                        eng.generate_shared(ids3[:, :4], tiles(3, 2), sfx2, max_new_tokens=1, eos_token_id=(), sampling=sp, logprobs=1),
+                        eng.generate_shared(ids3[:, :4], tiles(3, 2), sfx2, max_new_tokens=1, eos_token_id=()))
+    out["generate_shared_one_suffix_and_one_token"] = shared_small()
+
+    def shared_decode(sampling, k):                   # decode="shared" needs 4 query heads per KV head (the 2 : 1 micro configuration is refused)
+        cfg = micro_config()
+        cfg.text_config = TextConfig(hidden_size=512, intermediate_size=128, num_hidden_layers=2, num_attention_heads=4,
+                                     num_key_value_heads=1, vocab_size=256, rope_scaling=RopeScaling())
+        eng = LeopardEngine(cfg, EngineWeights.build(cfg, SynthSource(cfg, ops, "cpu", torch.float16), torch.float16), ops=ops, device="cpu")
+        return lambda: eng.generate_shared(ids3[:, :4], tiles(3, 2), sfx2 + [torch.tensor([[21]])], max_new_tokens=11, eos_token_id=(),
+                                           sampling=sampling, decode="shared", logprobs=k)
+    out["generate_shared_decode_shared_greedy"] = shared_decode(None, None)
+    out["generate_shared_decode_shared_sampled_logprobs2"] = shared_decode(sp, 2)
+
+    def idefics2_surface(kw):
+        from leopard_amd.idefics2 import Idefics2SynthSource
+        from leopard_amd.idefics2_compat import Idefics2ForConditionalGeneration
+        cfg, images, ids = idefics2_micro()
+        m = Idefics2ForConditionalGeneration(cfg, lambda dev, dt: Idefics2SynthSource(cfg, ops, dev, dt), torch.float16, ops).to("cpu")
+        H, W = max(im.shape[1] for im in images), max(im.shape[2] for im in images)
+        pix, mask = torch.zeros(1, len(images), 3, H, W), torch.zeros(1, len(images), H, W, dtype=torch.int64)
+        for i, im in enumerate(images):
+            pix[0, i, :, :im.shape[1], :im.shape[2]] = im
+            mask[0, i, :im.shape[1], :im.shape[2]] = 1
+        return lambda: m.generate(ids, pixel_values=pix, pixel_attention_mask=mask, max_new_tokens=4, eos_token_id=[], **kw)
+    out["idefics2_surface_generate_greedy"] = idefics2_surface({})
+    out["idefics2_surface_generate_sampled_logprobs2"] = idefics2_surface(dict(do_sample=True, temperature=0.8, top_k=20, top_p=0.9, seed=11,
+                                                                               logprobs=2))
     return out
 
 
@@ -241,7 +315,7 @@ def main():
             os.makedirs(args.dump, exist_ok=True)
             with open(os.path.join(args.dump, name + ".txt"), "w") as f:
                 f.write(text + "\n")
-        print(f"{name:34s} {len(rec.calls):6d} calls  sha256 {hashlib.sha256(text.encode()).hexdigest()[:16]}")
+        print(f"{name:48s} {len(rec.calls):6d} calls  sha256 {hashlib.sha256(text.encode()).hexdigest()[:16]}")
 
 
 if __name__ == "__main__":
