@@ -553,8 +553,9 @@ int lmi_lm_head_last(const void* W, const float* x, const int64_t* rows, const f
                      int N, int K, int ldw, int ldx, int ldo, int dtype, void* stream);
 
 /* Final RMSNorm of a GATHERED set of rows (the head of scoring, LeopardEngine.score): out[r] = T(w * (x[rows[r]] * rstd)) with the element
- * arithmetic of lmi_rmsnorm — the bits lmi_rmsnorm writes for that row in a pass over the whole stream.  x fp32 [., ldx], rows int64 [n_rows]
- * on device, out T [n_rows, ldo]; D % 8 == 0, D <= 4096; dtype LMI_F16 | LMI_BF16. */
+ * arithmetic of lmi_rmsnorm — the bits lmi_rmsnorm writes for that row in a pass over a stream of more than 32 rows (below that lmi_rmsnorm
+ * sums the squares in another order, and the last bit may differ).  x fp32 [., ldx], rows int64 [n_rows] on device, out T [n_rows, ldo];
+ * D % 8 == 0, D <= 4096; dtype LMI_F16 | LMI_BF16. */
 int lmi_rmsnorm_rows(const float* x, const int64_t* rows, const float* w, void* out, int n_rows, int D, int ldx, int ldo, float eps, int dtype,
                      void* stream);
 

@@ -1843,8 +1843,9 @@ int lmi_rmsnorm_rows(const float* x, const int64_t* rows, const float* w, void* 
         !aligned16(out))
         return fail(LMI_EINVAL, "lmi_rmsnorm_rows: bad argument (n_rows=%d D=%d ldx=%d ldo=%d; D%%8==0, D<=4096)", n_rows, D, ldx, ldo);
     if (n_rows == 0) return LMI_OK;
-    // always one wave per row (norm_kernel, lmi_rmsnorm's path for M > 32): the gathered rows get the bits lmi_rmsnorm gives them in a pass
-    // over the whole stream, however few they are
+    // always one wave per row (norm_kernel, lmi_rmsnorm's path for M > 32), however few rows are gathered: they get the bits lmi_rmsnorm gives
+    // them in a pass over a stream of MORE THAN 32 rows.  (At 32 rows or fewer lmi_rmsnorm takes norm_rows_kernel, which adds four wave
+    // partials: another summation order, so the last bit of a row can differ from what this entry writes.)
     const int grid = (n_rows + 3) / 4;
 #define LMI_NORM_ROWS(T_)                                                                                                                   \
     do {                                                                                                                                    \

@@ -1565,8 +1565,9 @@ class LeopardEngine:
             row0 += n
 
     def _score_head(self, x: torch.Tensor, rows: torch.Tensor, targets: torch.Tensor):
-        """Final RMSNorm of the gathered rows (lmi_rmsnorm_rows: the bits lmi_rmsnorm gives them) -> head GEMM into ONE reusable fp32 chunk of
-        at most ``score_chunk_rows`` rows -> lmi_token_logprobs.  Peak extra memory: about one chunk, whatever the number of rows."""
+        """Final RMSNorm of the gathered rows (lmi_rmsnorm_rows: the bits lmi_rmsnorm gives them in a stream of more than 32 rows; a shorter stream
+        goes through lmi_rmsnorm's few-rows kernel, which may differ in the last bit) -> head GEMM into ONE reusable fp32 chunk of at most
+        ``score_chunk_rows`` rows -> lmi_token_logprobs.  Peak extra memory: about one chunk, whatever the number of rows."""
         ops, W, tc = self.ops, self.W, self.cfg.text_config
         n, D, Vp = rows.numel(), x.shape[1], W.lm_head.shape[0]
         C = max(1, min(int(self.score_chunk_rows), n))

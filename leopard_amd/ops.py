@@ -477,7 +477,9 @@ class Ops:
         return out
 
     def rmsnorm_rows(self, x, rows, w, out, eps):
-        """out[r] = rmsnorm(x[rows[r]]) as lmi_rmsnorm computes it (lmi_rmsnorm_rows).  x: fp32 [S, D]; rows: int64 [n] on device; out: T [n, D]."""
+        """out[r] = rmsnorm(x[rows[r]]) as lmi_rmsnorm computes it over a stream of more than 32 rows, whatever n is (lmi_rmsnorm_rows; at 32
+        rows or fewer lmi_rmsnorm runs its few-rows kernel, whose sum of squares is added in another order).  x: fp32 [S, D]; rows: int64 [n]
+        on device; out: T [n, D]."""
         n, D = out.shape
         assert x.dtype == torch.float32 and rows.dtype == torch.int64 and rows.numel() == n and rows.is_contiguous() and x.shape[1] == D
         self._check(self.lib.lmi_rmsnorm_rows(_ptr(x), _ptr(rows), _ptr(w), _ptr(out), n, D, x.stride(0), out.stride(0), float(eps),

@@ -10,6 +10,7 @@ import torch
 from leopard_amd import _lib
 from leopard_amd.synth import KIND_BIAS, KIND_NORM, KIND_WEIGHT, name_seed, synth_array
 from tests.emu_util import emu_ops
+from tests.row_kernels_ref import check_decode_advance_stop_rule_and_history, check_preprocess_rectangular_image
 
 DTYPES = [torch.float16, torch.bfloat16]
 
@@ -485,18 +486,7 @@ def test_gemm_addmat_row_index(ops):
 
 
 def test_preprocess_rectangular_image(ops):
-    n, H, W, P, ldo = 2, 45, 61, 14, 640                       # 3 x 4 patches, remainder pixels dropped
-    pix = rnd((n, 3, H, W), torch.float32, 94)
-    out = torch.full((n * 12, ldo), 7.0, dtype=torch.float16)
-    ops.preprocess_images(pix.contiguous(), out, P)
-    ref = torch.nn.functional.unfold(pix[:, :, :42, :56], kernel_size=P, stride=P).transpose(1, 2).reshape(n * 12, 588)
-    assert torch.equal(out[:, :588].float(), ref.to(torch.float16).float()) and out[:, 588:].abs().max() == 0
-    u8 = torch.from_numpy(np.random.default_rng(1).integers(0, 256, (1, H, W, 3), dtype=np.uint8))
-    out2 = torch.empty(12, ldo, dtype=torch.float16)
-    ops.preprocess_images(u8, out2, P)
-    from leopard_amd.tiler import siglip_normalize
-    ref2 = torch.nn.functional.unfold(torch.from_numpy(siglip_normalize(u8.numpy()))[:, :, :42, :56], kernel_size=P, stride=P)
-    assert torch.equal(out2[:, :588].float(), ref2.transpose(1, 2).reshape(12, 588).to(torch.float16).float())
+    check_preprocess_rectangular_image(ops, "cpu")                   # tests/row_kernels_ref.py: the device runs it too
 
 
 def test_gemm_tile_order_round_robin(ops):
@@ -1031,39 +1021,8 @@ def test_prefill_workspace_api(ops):
 
 def test_decode_advance_argmax_stop_rule_and_history(ops):
     """lmi_decode_advance: per-row argmax (lowest index on ties, suppressed ids excluded), history ring, stop rule (eos ids, budget) and the
-    frozen state of stopped sequences, against a plain restatement."""
-    B, V, ld, H = 5, 1003, 1024, 3                                  # 250 vector loads + a 3-element tail per row
-    g = torch.Generator().manual_seed(3)
-    logits = torch.randn(B, ld, generator=g)
-    logits[:, V:] = 100.0                                           # padding columns past the vocabulary must be ignored
-    logits[1, 17] = logits[1, 400] = 50.0                           # a tie: the lower index wins
-    logits[2, 5] = 60.0                                             # suppressed: the runner-up must be chosen
-    suppress = torch.tensor([5], dtype=torch.int64)
-    want = []
-    for b in range(B):
-        row = logits[b, :V].clone()
-        row[5] = float("-inf")
-        want.append(int(row.argmax()))
-    want[1] = 17
-    tok = torch.zeros(B, dtype=torch.int64)
-    pos = torch.tensor([10, 20, 30, 40, 50], dtype=torch.int32)
-    k_len = pos + 1
-    live = torch.tensor([1, 1, 0, 1, 1], dtype=torch.int32)         # sequence 2 already stopped
-    budget = torch.tensor([5, 1, 9, 7, 3], dtype=torch.int32)       # sequence 1 produces its last token now
-    eos = torch.tensor([want[3], -1], dtype=torch.int64)            # sequence 3 hits its eos
-    hist = torch.full((H, B), -7, dtype=torch.int64)
-    hist_pos = torch.tensor([0, 1, 2, 3, 4], dtype=torch.int32)
-    ops.decode_advance(logits, V, tok, pos, k_len=k_len, live=live, budget=budget, eos=eos, hist=hist, hist_pos=hist_pos, suppress=suppress)
-    assert tok.tolist() == want
-    assert live.tolist() == [1, 0, 0, 0, 1] and budget.tolist() == [4, 0, 9, 6, 2]
-    assert pos.tolist() == [11, 20, 30, 40, 51] and k_len.tolist() == [12, 21, 31, 41, 52]
-    assert hist_pos.tolist() == [1, 2, 3, 4, 5]
-    for b in range(B):
-        assert int(hist[b % H, b]) == want[b]
-    # the batch-1 form: no live / budget / history
-    t1, p1, k1 = torch.zeros(1, dtype=torch.int64), torch.tensor([7], dtype=torch.int32), torch.tensor([8], dtype=torch.int32)
-    ops.decode_advance(logits[4:5], V, t1, p1, k_len=k1)
-    assert int(t1) == int(logits[4, :V].argmax()) and int(p1) == 8 and int(k1) == 9
+    frozen state of stopped sequences, against a plain restatement (the case lives in tests/row_kernels_ref.py: the device runs it too)."""
+    check_decode_advance_stop_rule_and_history(ops, "cpu")
 
 
 @pytest.mark.parametrize("cfg", [-1, 0, 3, 6, 10])

@@ -13,9 +13,9 @@ from leopard_amd.ops import Lo4Act, Lo4Weight, lo4_k4
 from leopard_amd.weights import interleave_gate_up, rope_permute_rows
 from oracle import leopard_oracle as O
 from tests.emu_util import emu_ops
+from tests.row_kernels_ref import assert_lo4_norm_output, decode_img
 
 DTYPES = [torch.float16, torch.bfloat16]
-E2M1 = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
 
 
 @pytest.fixture(scope="module")
@@ -28,17 +28,6 @@ def ops():
 def rnd(shape, dtype, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return (torch.randn(shape, generator=g) * scale).to(dtype)
-
-
-def decode_img(img: torch.Tensor, sc: torch.Tensor, K: int, per_row: bool = False) -> torch.Tensor:
-    """fp4 image [M, K4 / 2] bytes + E8M0 scales ([M, K4 / 32] or [M] with per_row) -> fp32 [M, K] (independent of the kernels)."""
-    M, half = img.shape
-    b = img.to(torch.int64)
-    codes = torch.stack([b & 15, b >> 4], dim=-1).reshape(M, half * 2)           # element k in nibble k & 1 of byte k >> 1
-    val = E2M1[codes & 7] * torch.where((codes & 8) != 0, -1.0, 1.0)
-    s = torch.exp2(sc.to(torch.float32) - 127.0)
-    s = s[:, None].expand(M, half * 2) if per_row else s[:, :half * 2 // 32].repeat_interleave(32, dim=1)
-    return (val * s)[:, :K]
 
 
 def eps(dtype):
@@ -90,15 +79,8 @@ def test_norm_lo4_hands_over_the_same_16_bit_rows_plus_their_residual(ops, dtype
     ops.norm_lo4(x, w, b, act, 1e-5)
     plain = torch.empty(M, D, dtype=dtype)
     (ops.rmsnorm(x, w, plain, 1e-5) if rms else ops.layernorm(x, w, b, plain, 1e-5))
-    assert torch.equal(act.hi, plain)                                     # the 16-bit operand is the one the fast schedule hands over
     y = (x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + 1e-5) * w) if rms else torch.nn.functional.layer_norm(x, (D,), w, b, 1e-5)
-    lo = decode_img(act.img, act.sc, D)
-    before = (y - act.hi.float()).pow(2).mean().sqrt().item()
-    after = (y - act.hi.float() - lo).pow(2).mean().sqrt().item()
-    assert after < 0.25 * before, (before, after)
-    k4 = lo4_k4(D)
-    if k4 > D:
-        assert act.img[:, D // 2:].abs().max() == 0 and act.sc[:, D // 32:k4 // 32].abs().max() == 0
+    assert_lo4_norm_output(act.hi, act.img, act.sc, plain, y, D)      # tests/row_kernels_ref.py: lmi_add_rmsnorm_lo4 owes the same
 
 
 def _operands(M, N, K, dtype, seed):

@@ -8,26 +8,14 @@ import pytest
 import torch
 
 from tests.emu_util import emu_ops
+from tests import row_kernels_ref as R
+from tests.row_kernels_ref import HEAD, gapped_row
 from tests.sampling_ref import chi2_ok, draw_many, kept_probs, kept_set
 
 
 @pytest.fixture(scope="module")
 def ops():
     return emu_ops()
-
-
-def gapped_row(V: int, head, seed: int = 0, ld: int = None) -> torch.Tensor:
-    """A logits row whose top tokens sit at scattered indices with the given values; the rest far below."""
-    g = torch.Generator().manual_seed(seed)
-    row = torch.full((ld or V,), 100.0)                               # padding past the vocabulary must never be drawn
-    row[:V] = -20.0 + torch.rand(V, generator=g)
-    where = torch.randperm(V, generator=g)[:len(head)]
-    for i, v in zip(where.tolist(), head):
-        row[i] = v
-    return row
-
-
-HEAD = [4.0, 3.6, 3.5, 3.0, 2.9, 2.2, 2.0, 1.1, 1.0, 0.2, -0.5, -3.0]
 
 
 @pytest.mark.parametrize("T,k,p", [(1.0, 5, 1.0), (1.0, 0, 0.8), (1.0, 6, 0.7), (0.5, 0, 0.9), (2.0, 8, 1.0), (1.0, 0, 0.0),
@@ -46,22 +34,7 @@ def test_kept_set_matches_float64_reference(ops, T, k, p):
 
 
 def test_kept_set_ties_keep_the_lower_indices(ops):
-    V = 512
-    row = torch.full((V,), -200.0)
-    tie = [7, 40, 41, 300, 301, 450]
-    row[tie] = 2.0
-    row[100] = 3.0
-    # top-k = 3: 100 plus the two lowest tied indices
-    draws = draw_many(ops, row, V, 1.0, 3, 1.0, n_rows=64, n_steps=6)
-    assert set(draws.tolist()) == {100, 7, 40} == set(kept_set(row, V, 1.0, 3, 1.0))
-    # top-p alone over six equal tokens: mass 1/2 -> exactly three, the lowest indices
-    row2 = torch.full((V,), -200.0)                                 # (no mass outside the tie group: the cut lands exactly on 1/2)
-    row2[tie] = 1.0
-    draws = draw_many(ops, row2, V, 1.0, 0, 0.5, n_rows=64, n_steps=6)
-    assert set(draws.tolist()) == {7, 40, 41} == set(kept_set(row2, V, 1.0, 0, 0.5))
-    # top-k and top-p together, the cut inside the tie group (0.375 of five: two)
-    draws = draw_many(ops, row2, V, 1.0, 5, 0.375, n_rows=64, n_steps=6)
-    assert set(draws.tolist()) == {7, 40} == set(kept_set(row2, V, 1.0, 5, 0.375))
+    R.check_kept_set_ties_keep_the_lower_indices(ops, "cpu")
 
 
 @pytest.mark.parametrize("T", [0.5, 1.0, 2.0])
@@ -78,82 +51,19 @@ def test_distribution_chi_square(ops, T):
 
 
 def test_draw_depends_on_seed_step_and_row_only(ops):
-    V = 777
-    g = torch.Generator().manual_seed(5)
-    rows = torch.randn(8, 800, generator=g) * 2
-    def call(logits, seeds, steps, T=0.9, k=40, p=0.95):
-        B = logits.shape[0]
-        tok = torch.zeros(B, dtype=torch.int64)
-        st = torch.tensor(steps, dtype=torch.int32)
-        ops.decode_sample(logits, V, torch.full((B,), T), torch.full((B,), k, dtype=torch.int32), torch.full((B,), p),
-                          torch.tensor(seeds, dtype=torch.int64), st, tok, torch.zeros(B, dtype=torch.int32))
-        return tok.tolist()
-    alone = [call(rows[5:6].clone(), [123456789012345], [s])[0] for s in range(40)]
-    seeds = [1, 2, 3, 4, 5, 123456789012345, 7, 8]
-    batched = [call(rows.clone(), seeds, [s] * 8)[5] for s in range(40)]
-    assert alone == batched
-    other = [call(rows[5:6].clone(), [987654321], [s])[0] for s in range(40)]
-    assert other != alone
-    assert len(set(alone)) > 3                                        # it does sample
+    R.check_draw_depends_on_seed_step_and_row_only(ops, "cpu")
 
 
 def test_suppressed_ids_are_never_drawn(ops):
-    V = 600
-    row = gapped_row(V, HEAD, seed=2)
-    top = kept_set(row, V, 1.0, 3, 1.0)
-    sup = torch.tensor(top[:2], dtype=torch.int64)
-    draws = draw_many(ops, row, V, 1.0, 4, 1.0, n_rows=64, n_steps=8, suppress=sup)
-    want = kept_set(row, V, 1.0, 4, 1.0, suppress=top[:2])
-    assert not (set(draws.tolist()) & set(top[:2])) and set(draws.tolist()) == set(want)
+    R.check_suppressed_ids_are_never_drawn(ops, "cpu")
 
 
 def test_top_k_1_is_decode_advance_and_shares_its_stop_rule(ops):
-    """top_k = 1 gives decode_advance's argmax (its tie and suppress rules), and the history ring, budget, eos, live mask and position
-    advance are those of test_decode_advance_argmax_stop_rule_and_history; the step counter advances for live rows only."""
-    B, V, ld, H = 5, 1003, 1024, 3
-    g = torch.Generator().manual_seed(3)
-    logits = torch.randn(B, ld, generator=g)
-    logits[:, V:] = 100.0
-    logits[1, 17] = logits[1, 400] = 50.0
-    logits[2, 5] = 60.0
-    suppress = torch.tensor([5], dtype=torch.int64)
-    want = []
-    for b in range(B):
-        row = logits[b, :V].clone()
-        row[5] = float("-inf")
-        want.append(int(row.argmax()))
-    want[1] = 17
-    outs = []
-    for kernel in ("advance", "sample"):
-        tok = torch.zeros(B, dtype=torch.int64)
-        pos = torch.tensor([10, 20, 30, 40, 50], dtype=torch.int32)
-        k_len = pos + 1
-        live = torch.tensor([1, 1, 0, 1, 1], dtype=torch.int32)
-        budget = torch.tensor([5, 1, 9, 7, 3], dtype=torch.int32)
-        eos = torch.tensor([want[3], -1], dtype=torch.int64)
-        hist = torch.full((H, B), -7, dtype=torch.int64)
-        hist_pos = torch.tensor([0, 1, 2, 3, 4], dtype=torch.int32)
-        step = torch.tensor([3, 3, 3, 3, 3], dtype=torch.int32)
-        kw = dict(k_len=k_len, live=live, budget=budget, eos=eos, hist=hist, hist_pos=hist_pos, suppress=suppress)
-        if kernel == "advance":
-            ops.decode_advance(logits, V, tok, pos, **kw)
-        else:
-            ops.decode_sample(logits, V, torch.full((B,), 0.7), torch.ones(B, dtype=torch.int32), torch.full((B,), 0.9),
-                              torch.arange(B, dtype=torch.int64), step, tok, pos, **kw)
-            assert step.tolist() == [4, 4, 3, 4, 4]                  # the frozen row's counter stays
-        outs.append([t.tolist() for t in (tok, pos, k_len, live, budget, hist, hist_pos)])
-    assert outs[0] == outs[1]
-    assert outs[1][0] == want
-    assert outs[1][3] == [1, 0, 0, 0, 1] and outs[1][1] == [11, 20, 30, 40, 51]
+    R.check_top_k_1_is_decode_advance_and_shares_its_stop_rule(ops, "cpu")
 
 
 def test_rows_without_a_drawable_token_give_token_zero(ops):
-    row = torch.full((2, 64), float("-inf"))
-    row[1, :] = float("nan")
-    tok = torch.full((2,), 9, dtype=torch.int64)
-    ops.decode_sample(row, 64, torch.ones(2), torch.zeros(2, dtype=torch.int32), torch.full((2,), 0.5), torch.zeros(2, dtype=torch.int64),
-                      torch.zeros(2, dtype=torch.int32), tok, torch.zeros(2, dtype=torch.int32))
-    assert tok.tolist() == [0, 0]
+    R.check_rows_without_a_drawable_token_give_token_zero(ops, "cpu")
 
 
 # ---- the generate() surface: arguments, defaults, warnings (no kernel launch) -----------------------------------------------------------
