@@ -26,53 +26,53 @@
 namespace lmi {
 
 struct AttnArgs {
-    const void* q;            // [total_q, ...] head h at q + row*ldq + h*D      (elements of T)
-    const void* k;            // head kvh at k + row*ldk + kvh*D
-    const void* v;
-    void* out;                // [total_q, ...] head h at out + row*ldo + h*D
-    const int* cu_q;          // [nseq+1]
-    const int* cu_k;          // [nseq+1]
-    const int* k_len;         // optional [nseq] (LDS-DMA kernel only): sequence s's keys are rows [cu_k[s], cu_k[s] + k_len[s]) — a pooled,
-                              // strided KV cache of a decode batch, where cu_k holds the slots' first rows and only k_len changes per step
-    int ldq, ldk, ldv, ldo;
-    int n_heads, n_kv_heads;
-    float scale;              // softmax scale (head_dim^-0.5)
-    int window;               // sliding window (Mistral): query i sees keys j with i - j < window; 0 = unlimited
-    int n_qblocks;            // ceil(max_seqlen_q / ATT_BQ) (1-D grid decode of the LDS-DMA kernel)
+    const void* q = nullptr;          // [total_q, ...] head h at q + row*ldq + h*D      (elements of T)
+    const void* k = nullptr;          // head kvh at k + row*ldk + kvh*D
+    const void* v = nullptr;
+    void* out = nullptr;              // [total_q, ...] head h at out + row*ldo + h*D
+    const int* cu_q = nullptr;        // [nseq+1]
+    const int* cu_k = nullptr;        // [nseq+1]
+    const int* k_len = nullptr;       // optional [nseq] (LDS-DMA kernel only): sequence s's keys are rows [cu_k[s], cu_k[s] + k_len[s]) — a pooled,
+                                      // strided KV cache of a decode batch, where cu_k holds the slots' first rows and only k_len changes per step
+    int ldq = 0, ldk = 0, ldv = 0, ldo = 0;
+    int n_heads = 0, n_kv_heads = 0;
+    float scale = 0.f;                // softmax scale (head_dim^-0.5)
+    int window = 0;                   // sliding window (Mistral): query i sees keys j with i - j < window; 0 = unlimited
+    int n_qblocks = 0;                // ceil(max_seqlen_q / ATT_BQ) (1-D grid decode of the LDS-DMA kernel)
     // split-KV (decode: few query rows against a long cache): the key range is cut into n_splits chunks of split_tiles
     // 64-key tiles, each workgroup writes an unnormalised partial (O fp32, reference max, row sum) and
     // attn_combine_kernel merges them.  n_splits <= 1: single pass, normalised output straight to `out`.
-    int n_splits, split_tiles, part_rows;
-    float* part_o;            // [n_splits, part_rows, n_heads, D]
-    float* part_ml;           // [n_splits, part_rows, n_heads, 2]  (m, l)
-    float* out_f32;           // LDS-DMA kernel, optional: instead of `out`, the normalised output in fp32 [total_q, ...] (row stride ldo32) — the
-    int ldo32;                // split-operand precision mode hands it to lmi_split_hi_lo instead of rounding it to 16 bits here
-    void* out_fp8;            // LDS-DMA kernel, optional: instead of `out`, write e4m3(O * out_fp8_scale) bytes [total_q, ...] (row stride ldo8) —
-    float out_fp8_scale;      // the o_proj operand of the fp8 schedule straight from the attention epilogue (no conversion launch)
-    int ldo8;
+    int n_splits = 1, split_tiles = 0, part_rows = 0;
+    float* part_o = nullptr;          // [n_splits, part_rows, n_heads, D]
+    float* part_ml = nullptr;         // [n_splits, part_rows, n_heads, 2]  (m, l)
+    float* out_f32 = nullptr;         // LDS-DMA kernel, optional: instead of `out`, the normalised output in fp32 [total_q, ...] (row stride ldo32) — the
+    int ldo32 = 0;                    // split-operand precision mode hands it to lmi_split_hi_lo instead of rounding it to 16 bits here
+    void* out_fp8 = nullptr;          // LDS-DMA kernel, optional: instead of `out`, write e4m3(O * out_fp8_scale) bytes [total_q, ...] (row stride ldo8) —
+    float out_fp8_scale = 0.f;        // the o_proj operand of the fp8 schedule straight from the attention epilogue (no conversion launch)
+    int ldo8 = 0;
     // LDS-DMA kernel, optional (beside `out`): the MX fp4 image of the rounding residuals O - T(O) and its block scales, for the low-bit
     // correction phase of the projection that consumes `out` (gemm.h LO4).  The image has its OWN k order: head h occupies the 32-element
     // blocks [h * NDB, (h + 1) * NDB) — head_dim 128: the natural order; 72 / 96: every head padded to 96 (zero codes), so that no block
     // straddles two heads (= two workgroups); the projection's weight image is laid out the same way (leopard_amd.engine).
-    uint8_t* out4;            // [total_q, ld_out4 bytes]: head h, block db at byte (h * NDB + db) * 16
-    uint8_t* out4_scale;      // [total_q, ld_out4s]: byte h * NDB + db
-    int ld_out4, ld_out4s;
-    const uint8_t* row_sel;   // [total_q] or null: the rows whose image is wanted (gemm.h GemmArgs::row_sel); the others only get their 16-bit row
-    int gqa_pack;             // LDS-DMA kernel, decode: a workgroup's 4 waves take the 4 query heads of ONE kv head (32 query rows per block)
-    int check_k_extent;       // 1 = the launcher could not bound a sequence's K / V extent (< 4 GiB): the kernel checks (and traps)
+    uint8_t* out4 = nullptr;          // [total_q, ld_out4 bytes]: head h, block db at byte (h * NDB + db) * 16
+    uint8_t* out4_scale = nullptr;    // [total_q, ld_out4s]: byte h * NDB + db
+    int ld_out4 = 0, ld_out4s = 0;
+    const uint8_t* row_sel = nullptr; // [total_q] or null: the rows whose image is wanted (gemm.h GemmArgs::row_sel); the others only get their 16-bit row
+    int gqa_pack = 0;                 // LDS-DMA kernel, decode: a workgroup's 4 waves take the 4 query heads of ONE kv head (32 query rows per block)
+    int check_k_extent = 0;           // 1 = the launcher could not bound a sequence's K / V extent (< 4 GiB): the kernel checks (and traps)
     // LDS-DMA kernel, optional (the PREFIX instantiation, head_dim 128): a key range SHARED by every sequence of the launch, in front of the
     // sequence's own keys.  Sequence s sees [prefix rows 0 .. prefix_len) ; own rows cu_k[s] .. cu_k[s + 1)] with len_k[s] == len_q[s]: every
     // prefix key is visible to every query, the own range is causal.  The prefix is read in place (a KV cache filled once), never copied.
-    const void* k_prefix;     // head kvh at k_prefix + row*ldkp + kvh*D; null = no prefix
-    const void* v_prefix;
-    int ldkp, ldvp;
-    int prefix_len;           // P >= 1 (host integer); the SHARED instantiation: the capacity that bounds the device-resident length
+    const void* k_prefix = nullptr;   // head kvh at k_prefix + row*ldkp + kvh*D; null = no prefix
+    const void* v_prefix = nullptr;
+    int ldkp = 0, ldvp = 0;
+    int prefix_len = 0;               // P >= 1 (host integer); the SHARED instantiation: the capacity that bounds the device-resident length
     // Decode with a shared prefix (lmi_attn_decode_shared): two walks write their partials into one workspace and one merge reads them all.
     //   * prefix pass (the SHARED instantiation): ONE key range — k / v are the prefix rows [0, min(k_len[0], prefix_len)), the length in device
     //     memory — and query row r of q is the current token of sequence r (shared_rows of them, n_qblocks = ceil(shared_rows / 32) GQA-packed
     //     row blocks: one for a decode batch; lmi_attn_prefix_rows packs the rows of many short continuations, k_len == null: prefix_len rows);
     //   * own pass (cu_q == null): one query row per sequence, row s of q, against the pooled rows cu_k[s] .. cu_k[s] + k_len[s]).
-    int split_base = 0;       // the partials of this launch are splits split_base .. split_base + n_splits) of the workspace
+    int split_base = 0;               // the partials of this launch are splits split_base .. split_base + n_splits) of the workspace
     int shared_rows = 0;
 };
 

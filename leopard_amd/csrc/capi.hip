@@ -320,29 +320,30 @@ std::atomic<int> g_attn_split_tiles{0};      // decode: 64-key tiles per split-K
 std::atomic<int> g_attn_gqa_pack{1};         // decode: 1 = a workgroup's waves take the query heads of one kv head (A/B knob attn.gqa_pack)
 std::atomic<int> g_attn_dma{1};                          // 1 = LDS-DMA kernel (production), 0 = register-staged kernel (cross-checks)
 
-template <typename T, int D, bool CAUSAL>
-int launch_attn_dma(const AttnArgs& a, int n_seq, int max_q, void* stream) {
-    const int qblocks = (max_q + ATT_BQ - 1) / ATT_BQ;
+// 32-bit buffer offsets: `rows` rows of row stride ld (16-bit elements) and the last row's head must end below 4 GiB
+bool spans_4gib(long rows, int ld, int head_dim) { return (rows * ld + head_dim) * 2 >= (1L << 32); }
+
+// One attention launch on a 1-D grid.  The dynamic-LDS limit is raised per kernel instantiation, whichever entry launches it first.
+template <void (*KERNEL)(AttnArgs)>
+void launch_attn_1d(const AttnArgs& a, long grid, int block, int lds_limit, int lds_bytes, void* stream) {
     static std::atomic<uint64_t> attr_done{0};
-    allow_big_lds(attn_fwd_dma_kernel<T, D, CAUSAL>, 160 * 1024, attr_done);
-    AttnArgs b = a;
-    b.n_qblocks = qblocks;
-    LMI_LAUNCH((attn_fwd_dma_kernel<T, D, CAUSAL>), dim3(qblocks * a.n_heads * n_seq), dim3(ATT_THREADS),
-               AttnDmaGeom<D>::SMEM + g_attn_lds_pad, stream, b);
-    return check_launch("lmi_attn_varlen_fwd");
+    allow_big_lds(KERNEL, lds_limit, attr_done);
+    LMI_LAUNCH(KERNEL, dim3((unsigned)grid), dim3(block), lds_bytes, stream, a);
 }
 
-// Two-range keys (AttnArgs::k_prefix): always the LDS-DMA kernel, its PREFIX instantiation — no other attention kernel knows the prefix range.
-template <typename T>
-int launch_attn_prefix(const AttnArgs& a, int n_seq, int max_q, void* stream) {
-    const int qblocks = (max_q + ATT_BQ - 1) / ATT_BQ;
-    static std::atomic<uint64_t> attr_done{0};
-    allow_big_lds(attn_fwd_dma_kernel<T, 128, true, false, true>, 160 * 1024, attr_done);
-    AttnArgs b = a;
-    b.n_qblocks = qblocks;
-    LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true, false, true>), dim3(qblocks * a.n_heads * n_seq), dim3(ATT_THREADS),
-               AttnDmaGeom<128>::SMEM + g_attn_lds_pad, stream, b);
-    return check_launch("lmi_attn_prefix_fwd");
+// Prefill kernels whose 1-D grid is (query block, head, sequence) with bq query rows per block
+template <void (*KERNEL)(AttnArgs)>
+int launch_attn_qblocks(AttnArgs a, int n_seq, int max_q, int bq, int block, int lds_limit, int lds_bytes, const char* who, void* stream) {
+    a.n_qblocks = (max_q + bq - 1) / bq;
+    launch_attn_1d<KERNEL>(a, a.n_qblocks * a.n_heads * n_seq, block, lds_limit, lds_bytes, stream);
+    return check_launch(who);
+}
+
+// The LDS-DMA kernel.  Two-range keys (AttnArgs::k_prefix) take its PREFIX instantiation — no other attention kernel knows the prefix range.
+template <typename T, int D, bool CAUSAL, bool PREFIX = false>
+int launch_attn_dma(const AttnArgs& a, int n_seq, int max_q, const char* who, void* stream) {
+    return launch_attn_qblocks<attn_fwd_dma_kernel<T, D, CAUSAL, false, PREFIX>>(a, n_seq, max_q, ATT_BQ, ATT_THREADS, 160 * 1024,
+                                                                                AttnDmaGeom<D>::SMEM + g_attn_lds_pad, who, stream);
 }
 
 // Software-pipelined attention (attention64.h): long self-attention prefills at head_dim 128 writing the plain 16-bit output.  OPT-IN
@@ -355,20 +356,14 @@ std::atomic<int> g_attn_rows64_min{1024};
 template <typename T, bool CAUSAL, int NBLK>
 int launch_attn_r64(const AttnArgs& a, int n_seq, int max_q, void* stream) {
     typedef Attn64Geom<NBLK> G;
-    const int qblocks = (max_q + G::BQ - 1) / G::BQ;
-    static std::atomic<uint64_t> attr_done{0};
-    allow_big_lds(attn_fwd_r64_kernel<T, CAUSAL, NBLK>, G::SMEM, attr_done);
-    AttnArgs b = a;
-    b.n_qblocks = qblocks;
-    LMI_LAUNCH((attn_fwd_r64_kernel<T, CAUSAL, NBLK>), dim3(qblocks * a.n_heads * n_seq), dim3(G::NT), G::SMEM, stream, b);
-    return check_launch("lmi_attn_varlen_fwd");
+    return launch_attn_qblocks<attn_fwd_r64_kernel<T, CAUSAL, NBLK>>(a, n_seq, max_q, G::BQ, G::NT, G::SMEM, G::SMEM, "lmi_attn_varlen_fwd", stream);
 }
 template <typename T, int D>
 bool attn_r64_applies(const AttnArgs& a, int max_q, int use_tr) {
     if (D != 128 || !use_tr || !g_attn_dma.load() || !g_attn_rows64.load() || max_q < g_attn_rows64_min.load()) return false;
     if (!a.out || a.out_fp8 || a.out_f32 || a.out4 || a.n_splits > 1 || a.k_len || a.gqa_pack || a.check_k_extent || a.k_prefix) return false;   // self-attention, 16-bit output only
     // the ring requests tiles up to two past the end (range-checked to zeros): their 32-bit offsets must not wrap
-    return ((long)(max_q + 4 * ATT_BKV) * a.ldk + D) * 2 < (1L << 32) && ((long)(max_q + 4 * ATT_BKV) * a.ldv + D) * 2 < (1L << 32);
+    return !spans_4gib(max_q + 4 * ATT_BKV, a.ldk, D) && !spans_4gib(max_q + 4 * ATT_BKV, a.ldv, D);
 }
 
 template <typename T, int D>
@@ -381,7 +376,8 @@ int dispatch_attn(const AttnArgs& a, int n_seq, int max_q, int causal, int use_t
         }
     }
     if (use_tr && g_attn_dma)
-        return causal ? launch_attn_dma<T, D, true>(a, n_seq, max_q, stream) : launch_attn_dma<T, D, false>(a, n_seq, max_q, stream);
+        return causal ? launch_attn_dma<T, D, true>(a, n_seq, max_q, "lmi_attn_varlen_fwd", stream)
+                      : launch_attn_dma<T, D, false>(a, n_seq, max_q, "lmi_attn_varlen_fwd", stream);
     if (causal) return use_tr ? launch_attn<T, D, true, true>(a, n_seq, max_q, stream)
                               : launch_attn<T, D, true, false>(a, n_seq, max_q, stream);
     return use_tr ? launch_attn<T, D, false, true>(a, n_seq, max_q, stream)
@@ -542,23 +538,25 @@ static int decode_grid_heads(int n_heads, int n_kv_heads, int max_q) {
     return (g_attn_gqa_pack.load() && n_heads == 4 * n_kv_heads && max_q <= 32) ? n_kv_heads : n_heads;
 }
 
+// One split-KV launch sequence for every decode-shaped entry: [prefix pass,] own pass, merge.  `pre` (nullable) and `own` write their
+// partials into one workspace — splits 0 .. pre->n_splits) and own.split_base .. + own.n_splits) — and attn_combine_kernel reads them all.
+// A pass's grid is one workgroup per (query block, kv head if GQA-packed else query head, sequence, split): `pre` has ONE key range, `own`
+// has n_seq.  The merge has one workgroup per (row, head) of `rows` rows, writes own.out (the hi+lo pair form when lo_rows != 0) and, when
+// asked, the fp32 rows.
 template <typename T>
-int attn_decode_impl(AttnArgs a, int n_seq, int max_q, int q_rows, void* out, int ldo, void* stream, int lo_rows = 0) {
-    static std::atomic<uint64_t> attr_done{0};
-    static std::atomic<uint64_t> attr_done_s{0};
-    allow_big_lds(attn_fwd_dma_kernel<T, 128, true>, 160 * 1024, attr_done);
-    allow_big_lds(attn_fwd_dma_kernel<T, 128, true, true>, 160 * 1024, attr_done_s);
-    // GQA-packed blocks when a kv head serves exactly 4 query heads (Llama-3.1-8B, Mistral-7B) and a sequence has at most 32 query rows
-    a.gqa_pack = decode_grid_heads(a.n_heads, a.n_kv_heads, max_q) != a.n_heads ? 1 : 0;
-    a.n_qblocks = a.gqa_pack ? (max_q + 31) / 32 : (max_q + ATT_BQ - 1) / ATT_BQ;
-    const dim3 grid(a.n_qblocks * (a.gqa_pack ? a.n_kv_heads : a.n_heads) * n_seq * a.n_splits);
+int launch_attn_split_kv(const AttnArgs* pre, const AttnArgs& own, int n_seq, int rows, int lo_rows, float* out_f32, int ldo32, const char* who,
+                         void* stream) {
+    const auto grid = [](const AttnArgs& a, int seqs) { return (long)a.n_qblocks * (a.gqa_pack ? a.n_kv_heads : a.n_heads) * seqs * a.n_splits; };
+    const int limit = 160 * 1024, lds = AttnDmaGeom<128>::SMEM;
+    // prefix pass (the SHARED instantiation): every tile is read once by all the rows of a block: non-temporal
+    if (pre) launch_attn_1d<attn_fwd_dma_kernel<T, 128, false, true, false, true>>(*pre, grid(*pre, 1), ATT_THREADS, limit, lds, stream);
     // GQA-packed blocks read every K / V tile exactly once: non-temporal loads; head-per-block launches re-read them from L2 (4 query heads)
-    if (a.gqa_pack && g_attn_stream_kv.load()) LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, a);
-    else LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, a);
-    const long items = (long)q_rows * a.n_heads;
-    LMI_LAUNCH((attn_combine_kernel<T, 128>), dim3((unsigned)items), dim3(256), 0, stream, (const float*)a.part_o,
-               (const float*)a.part_ml, (T*)out, a.cu_q, n_seq, a.n_heads, a.n_splits, a.part_rows, ldo, a.scale, lo_rows, (float*)nullptr, 0);
-    return check_launch("lmi_attn_decode_fwd");
+    if (own.gqa_pack && g_attn_stream_kv.load()) launch_attn_1d<attn_fwd_dma_kernel<T, 128, true, true>>(own, grid(own, n_seq), ATT_THREADS, limit, lds, stream);
+    else launch_attn_1d<attn_fwd_dma_kernel<T, 128, true>>(own, grid(own, n_seq), ATT_THREADS, limit, lds, stream);
+    LMI_LAUNCH((attn_combine_kernel<T, 128>), dim3((unsigned)((long)rows * own.n_heads)), dim3(256), 0, stream, (const float*)own.part_o,
+               (const float*)own.part_ml, (T*)own.out, own.cu_q, n_seq, own.n_heads, (pre ? pre->n_splits : 0) + own.n_splits, own.part_rows, own.ldo,
+               own.scale, lo_rows, out_f32, ldo32);
+    return check_launch(who);
 }
 
 // ---- decode attention behind a shared prefix: prefix pass + own pass + one merge -----------------------------------------------------
@@ -585,50 +583,65 @@ static SharedSplits decode_shared_splits(int n_kv_heads, int max_prefix_len, int
     return g;
 }
 
-template <typename T>
-int attn_decode_shared_impl(AttnArgs pre, AttnArgs own, int n_seq, int q_rows, void* out, int ldo, void* stream, int lo_rows) {
-    static std::atomic<uint64_t> attr_done{0};
-    static std::atomic<uint64_t> attr_done_s{0};
-    static std::atomic<uint64_t> attr_done_p{0};
-    allow_big_lds(attn_fwd_dma_kernel<T, 128, true>, 160 * 1024, attr_done);
-    allow_big_lds(attn_fwd_dma_kernel<T, 128, true, true>, 160 * 1024, attr_done_s);
-    allow_big_lds(attn_fwd_dma_kernel<T, 128, false, true, false, true>, 160 * 1024, attr_done_p);
-    // prefix pass: one GQA-packed row block (row r = sequence r) per (kv head, split); every tile is read once by the whole batch: non-temporal
-    LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, false, true, false, true>), dim3(pre.n_kv_heads * pre.n_splits), dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, pre);
-    // own pass: the pooled split-KV walk of lmi_attn_decode_pool, one query row per sequence
-    const dim3 grid(own.n_kv_heads * n_seq * own.n_splits);
-    if (g_attn_stream_kv.load()) LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, own);
-    else LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, own);
-    const long items = (long)n_seq * own.n_heads;
-    LMI_LAUNCH((attn_combine_kernel<T, 128>), dim3((unsigned)items), dim3(256), 0, stream, (const float*)own.part_o, (const float*)own.part_ml, (T*)out,
-               (const int*)nullptr, n_seq, own.n_heads, pre.n_splits + own.n_splits, own.part_rows, ldo, own.scale, lo_rows, (float*)nullptr, 0);
-    (void)q_rows;
-    return check_launch("lmi_attn_decode_shared");
-}
-
-// ---- row-packed two-range attention (lmi_attn_prefix_rows): the three launches above with R packed query rows --------------------------------
+// ---- row-packed two-range attention (lmi_attn_prefix_rows): the same three launches with R packed query rows ----------------------------------
 // Prefix pass: ceil(R / 32) GQA-packed row blocks per (kv head, split) — every prefix key is visible to every row, so rows of different
 // continuations share a tile and the prefix is read once per 32 rows.  Own pass: every row is a "sequence" of one query row whose keys are
 // the pooled rows k_begin[r] .. k_begin[r] + k_len[r]) — the caller writes causality into k_len.  One merge over all splits, which also
 // writes the fp32 rows when asked.  The split geometry is decode_shared_splits' (a function of prefix_len, max_k_len and the head counts,
 // never of R or of another row's range): a row alone and the same row among others get the same bits.
-template <typename T>
-int attn_prefix_rows_impl(AttnArgs pre, AttnArgs own, int n_rows, void* out, int ldo, float* out32, int ldo32, void* stream) {
-    static std::atomic<uint64_t> attr_done{0};
-    static std::atomic<uint64_t> attr_done_s{0};
-    static std::atomic<uint64_t> attr_done_p{0};
-    allow_big_lds(attn_fwd_dma_kernel<T, 128, true>, 160 * 1024, attr_done);
-    allow_big_lds(attn_fwd_dma_kernel<T, 128, true, true>, 160 * 1024, attr_done_s);
-    allow_big_lds(attn_fwd_dma_kernel<T, 128, false, true, false, true>, 160 * 1024, attr_done_p);
-    LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, false, true, false, true>), dim3(pre.n_kv_heads * pre.n_splits * pre.n_qblocks), dim3(ATT_THREADS),
-               AttnDmaGeom<128>::SMEM, stream, pre);
-    const dim3 grid(own.n_kv_heads * n_rows * own.n_splits);
-    if (g_attn_stream_kv.load()) LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, own);
-    else LMI_LAUNCH((attn_fwd_dma_kernel<T, 128, true>), grid, dim3(ATT_THREADS), AttnDmaGeom<128>::SMEM, stream, own);
-    const long items = (long)n_rows * own.n_heads;
-    LMI_LAUNCH((attn_combine_kernel<T, 128>), dim3((unsigned)items), dim3(256), 0, stream, (const float*)own.part_o, (const float*)own.part_ml, (T*)out,
-               (const int*)nullptr, n_rows, own.n_heads, pre.n_splits + own.n_splits, own.part_rows, ldo, own.scale, 0, out32, ldo32);
-    return check_launch("lmi_attn_prefix_rows");
+
+// Workspace of both: the partials of every split of the two passes
+static int64_t two_range_workspace_bytes(int rows, int n_heads, int head_dim, int prefix_len, int max_k) {
+    if (rows < 0 || n_heads <= 0 || (n_heads & 3) || head_dim <= 0 || prefix_len < 1 || max_k < 0) return -1;
+    const SharedSplits g = decode_shared_splits(n_heads / 4, prefix_len, max_k);
+    return (int64_t)(g.pre_n + g.own_n) * rows * n_heads * (head_dim + 2) * 4;
+}
+
+// The words in which the two entries state the rules they share
+struct TwoRangeWords { const char *who, *fp32_strides, *prefix_len, *own_span, *max_k; };
+
+// Refusals common to the two entries, in the order both have always tested them, then the argument pair: `pre` walks the shared prefix rows
+// [0, prefix_len) for `rows` query rows packed 32 to a block, `own` walks row r's pooled keys k_begin[r] .. k_begin[r] + k_len[r]); the
+// partials of both land in one workspace of part_rows rows.  `size_rule` is the entry's own refusals about its sizes, tested after the head
+// counts.  The entry adds what only it knows (the prefix length in device memory) and launches.
+template <typename SizeRule>
+int two_range_args(const TwoRangeWords& w, SizeRule size_rule, const void* q, const void* k_prefix, const void* v_prefix, const void* k, const void* v,
+                   void* out, float* out_f32, const int* k_begin, const int* k_len, int rows, int part_rows, int prefix_len, int max_k, int n_heads,
+                   int n_kv_heads, int head_dim, int ldq, int ldkp, int ldvp, int ldk, int ldv, int ldo, int ldo32, float scale, void* workspace,
+                   int64_t workspace_bytes, AttnArgs& pre, AttnArgs& own) {
+    const char* who = w.who;
+    if (!q || !k_prefix || !v_prefix || !k || !v || !out || !k_begin || !k_len || !workspace) return fail(LMI_EINVAL, "%s: null pointer", who);
+    if (head_dim != 128) return fail(LMI_EINVAL, "%s: head_dim %d (only 128)", who, head_dim);
+    if (n_heads <= 0 || n_kv_heads <= 0 || n_heads != 4 * n_kv_heads)
+        return fail(LMI_EINVAL, "%s: needs n_heads == 4 * n_kv_heads (a workgroup's 4 waves take the query heads of one kv head), got %d / %d", who, n_heads, n_kv_heads);
+    if (int rc = size_rule()) return rc;
+    if ((ldq & 7) || (ldkp & 7) || (ldvp & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) || ldq < n_heads * head_dim || ldo < n_heads * head_dim ||
+        ldkp < n_kv_heads * head_dim || ldvp < n_kv_heads * head_dim || ldk < n_kv_heads * head_dim || ldv < n_kv_heads * head_dim ||
+        (out_f32 && ((ldo32 & 3) || ldo32 < n_heads * head_dim)))
+        return fail(LMI_EINVAL, "%s: row strides must be multiples of 8%s and at least the heads' width", who, w.fp32_strides);
+    if (!aligned16(q) || !aligned16(k_prefix) || !aligned16(v_prefix) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(workspace) ||
+        (out_f32 && !aligned16(out_f32)))
+        return fail(LMI_EINVAL, "%s: alignment", who);
+    if (spans_4gib(prefix_len, ldkp, head_dim) || spans_4gib(prefix_len, ldvp, head_dim))
+        return fail(LMI_EINVAL, "%s: the prefix K / V rows span >= 4 GiB (%s %d, ldkp %d, ldvp %d)", who, w.prefix_len, prefix_len, ldkp, ldvp);
+    if (spans_4gib(max_k, ldk, head_dim) || spans_4gib(max_k, ldv, head_dim))
+        return fail(LMI_EINVAL, "%s: one %s >= 4 GiB (%s %d, ldk %d, ldv %d)", who, w.own_span, w.max_k, max_k, ldk, ldv);
+    const int64_t need = two_range_workspace_bytes(part_rows, n_heads, head_dim, prefix_len, max_k);
+    if (workspace_bytes < need) return fail(LMI_EINVAL, "%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+    const SharedSplits g = decode_shared_splits(n_kv_heads, prefix_len, max_k);
+    AttnArgs a;
+    a.q = q; a.out = out; a.ldq = ldq; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale;
+    a.gqa_pack = 1; a.n_qblocks = 1;                               // own pass: one query row per "sequence"
+    a.part_rows = part_rows;
+    a.part_o = (float*)workspace;
+    a.part_ml = a.part_o + (size_t)(g.pre_n + g.own_n) * part_rows * n_heads * head_dim;
+    pre = own = a;
+    pre.k = k_prefix; pre.v = v_prefix; pre.ldk = ldkp; pre.ldv = ldvp; pre.prefix_len = prefix_len; pre.shared_rows = rows;
+    pre.n_qblocks = (rows + 31) / 32;                              // a decode batch (at most 32 sequences): one block
+    pre.n_splits = g.pre_n; pre.split_tiles = g.pre_tiles; pre.split_base = 0;
+    own.k = k; own.v = v; own.ldk = ldk; own.ldv = ldv; own.cu_k = k_begin; own.k_len = k_len;
+    own.n_splits = g.own_n; own.split_tiles = g.own_tiles; own.split_base = g.pre_n;
+    return LMI_OK;
 }
 
 std::atomic<int> g_skinny_coalesce{1};       // nn.Linear-layout weights of the M <= 16 kernel: 1 = coalescing lane order + ds_bpermute (LAYOUT 2), 0 = MFMA lane order
@@ -1225,15 +1238,13 @@ static int attn_varlen_entry(const char* who, const void* q, const void* k, cons
         return fail(LMI_EINVAL, "%s: the fp32 output needs the LDS-DMA kernel (use_tr), ldo32 %% 4 == 0 and a 16-byte aligned pointer", who);
     if (n_seq == 0 || max_seqlen_q == 0) return LMI_OK;
     AttnArgs a;
-    a.q = q; a.k = k; a.v = v; a.out = out; a.cu_q = cu_seqlens_q; a.cu_k = cu_seqlens_k; a.k_len = nullptr;
+    a.q = q; a.k = k; a.v = v; a.out = out; a.cu_q = cu_seqlens_q; a.cu_k = cu_seqlens_k;
     a.out_fp8 = out_fp8; a.ldo8 = ldo8; a.out_fp8_scale = out_fp8_scale; a.out_f32 = out_f32; a.ldo32 = ldo32;
     a.out4 = (uint8_t*)out4; a.out4_scale = (uint8_t*)out4_scale; a.ld_out4 = ld_out4; a.ld_out4s = ld_out4s; a.row_sel = row_sel;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale; a.window = window; a.n_qblocks = 0;
-    a.n_splits = 1; a.split_tiles = 0; a.part_rows = 0; a.part_o = nullptr; a.part_ml = nullptr; a.gqa_pack = 0;
-    a.k_prefix = nullptr; a.v_prefix = nullptr; a.ldkp = a.ldvp = 0; a.prefix_len = 0;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale; a.window = window;
     a.check_k_extent = 1;
     if (cu_seqlens_k == cu_seqlens_q) {                              // self-attention: the longest key sequence is max_seqlen_q
-        if (((long)max_seqlen_q * ldk + head_dim) * 2 >= (1L << 32) || ((long)max_seqlen_q * ldv + head_dim) * 2 >= (1L << 32))
+        if (spans_4gib(max_seqlen_q, ldk, head_dim) || spans_4gib(max_seqlen_q, ldv, head_dim))
             return fail(LMI_EINVAL, "%s: one sequence's K / V rows span >= 4 GiB (max_seqlen %d, ldk %d, ldv %d)", who, max_seqlen_q, ldk, ldv);
         a.check_k_extent = 0;
     }
@@ -1348,13 +1359,12 @@ static int attn_prefix_entry(const char* who, const void* q, const void* k, cons
         return fail(LMI_EINVAL, "%s: prefix + own K / V rows span >= 4 GiB (prefix_len %d, max_seqlen %d)", who, prefix_len, max_seqlen_q);
     if (n_seq == 0 || max_seqlen_q == 0) return LMI_OK;
     AttnArgs a;
-    a.q = q; a.k = k; a.v = v; a.out = out; a.cu_q = cu_seqlens; a.cu_k = cu_seqlens; a.k_len = nullptr;
-    a.out_fp8 = nullptr; a.ldo8 = 0; a.out_fp8_scale = 0.f; a.out_f32 = nullptr; a.ldo32 = 0;
+    a.q = q; a.k = k; a.v = v; a.out = out; a.cu_q = cu_seqlens; a.cu_k = cu_seqlens;
     a.out4 = (uint8_t*)out4; a.out4_scale = (uint8_t*)out4_scale; a.ld_out4 = ld_out4; a.ld_out4s = ld_out4s; a.row_sel = row_sel;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale; a.window = 0; a.n_qblocks = 0;
-    a.n_splits = 1; a.split_tiles = 0; a.part_rows = 0; a.part_o = nullptr; a.part_ml = nullptr; a.gqa_pack = 0; a.check_k_extent = 0;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale;
     a.k_prefix = k_prefix; a.v_prefix = v_prefix; a.ldkp = ldkp; a.ldvp = ldvp; a.prefix_len = prefix_len;
-    LMI_DISPATCH_T(dtype, (launch_attn_prefix<f16_t>(a, n_seq, max_seqlen_q, stream)), (launch_attn_prefix<bf16_t>(a, n_seq, max_seqlen_q, stream)));
+    LMI_DISPATCH_T(dtype, (launch_attn_dma<f16_t, 128, true, true>(a, n_seq, max_seqlen_q, "lmi_attn_prefix_fwd", stream)),
+                   (launch_attn_dma<bf16_t, 128, true, true>(a, n_seq, max_seqlen_q, "lmi_attn_prefix_fwd", stream)));
 }
 
 int lmi_attn_prefix_fwd(const void* q, const void* k, const void* v, const void* k_prefix, const void* v_prefix, int prefix_len, void* out,
@@ -1464,21 +1474,21 @@ static int attn_decode_entry(const char* who, const void* q, const void* k, cons
     const int64_t need = lmi_attn_decode_workspace_bytes(q_rows, n_heads, head_dim, max_seqlen_k);
     if (workspace_bytes < need) return fail(LMI_EINVAL, "%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
     if (n_seq == 0 || max_seqlen_q == 0 || q_rows == 0) return LMI_OK;
+    if (spans_4gib(max_seqlen_k, ldk, head_dim) || spans_4gib(max_seqlen_k, ldv, head_dim))
+        return fail(LMI_EINVAL, "%s: one sequence's K / V rows span >= 4 GiB (max_seqlen_k %d, ldk %d, ldv %d)", who, max_seqlen_k, ldk, ldv);
     AttnArgs a;
     a.q = q; a.k = k; a.v = v; a.out = out; a.cu_q = cu_seqlens_q; a.cu_k = cu_seqlens_k; a.k_len = k_len;
-    a.out_fp8 = nullptr; a.ldo8 = 0; a.out_fp8_scale = 0.f; a.out_f32 = nullptr; a.ldo32 = 0;
-    a.out4 = nullptr; a.out4_scale = nullptr; a.ld_out4 = a.ld_out4s = 0; a.row_sel = nullptr;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale; a.window = window;
-    a.k_prefix = nullptr; a.v_prefix = nullptr; a.ldkp = a.ldvp = 0; a.prefix_len = 0;
-    if (((long)max_seqlen_k * ldk + head_dim) * 2 >= (1L << 32) || ((long)max_seqlen_k * ldv + head_dim) * 2 >= (1L << 32))
-        return fail(LMI_EINVAL, "%s: one sequence's K / V rows span >= 4 GiB (max_seqlen_k %d, ldk %d, ldv %d)", who, max_seqlen_k, ldk, ldv);
-    a.check_k_extent = 0;
-    a.n_splits = decode_splits(max_seqlen_k, decode_grid_heads(n_heads, n_kv_heads, max_seqlen_q), &a.split_tiles);
+    // GQA-packed blocks when a kv head serves exactly 4 query heads (Llama-3.1-8B, Mistral-7B) and a sequence has at most 32 query rows
+    const int grid_heads = decode_grid_heads(n_heads, n_kv_heads, max_seqlen_q);
+    a.gqa_pack = grid_heads != n_heads ? 1 : 0;
+    a.n_qblocks = a.gqa_pack ? (max_seqlen_q + 31) / 32 : (max_seqlen_q + ATT_BQ - 1) / ATT_BQ;
+    a.n_splits = decode_splits(max_seqlen_k, grid_heads, &a.split_tiles);
     a.part_rows = q_rows;
     a.part_o = (float*)workspace;
     a.part_ml = a.part_o + (size_t)a.n_splits * q_rows * n_heads * head_dim;
-    LMI_DISPATCH_T(dtype, (attn_decode_impl<f16_t>(a, n_seq, max_seqlen_q, q_rows, out, ldo, stream, hl ? q_rows : 0)),
-                   (attn_decode_impl<bf16_t>(a, n_seq, max_seqlen_q, q_rows, out, ldo, stream, hl ? q_rows : 0)));
+    LMI_DISPATCH_T(dtype, (launch_attn_split_kv<f16_t>(nullptr, a, n_seq, q_rows, hl ? q_rows : 0, nullptr, 0, who, stream)),
+                   (launch_attn_split_kv<bf16_t>(nullptr, a, n_seq, q_rows, hl ? q_rows : 0, nullptr, 0, who, stream)));
 }
 
 int lmi_attn_decode_fwd(const void* q, const void* k, const void* v, void* out, const int* cu_seqlens_q, const int* cu_seqlens_k,
@@ -1499,50 +1509,30 @@ int lmi_attn_decode_pool(const void* q, const void* k, const void* v, void* out,
 }
 
 int64_t lmi_attn_decode_shared_workspace_bytes(int q_rows, int n_heads, int head_dim, int max_prefix_len, int max_seqlen_k) {
-    if (q_rows < 0 || n_heads <= 0 || (n_heads & 3) || head_dim <= 0 || max_prefix_len < 1 || max_seqlen_k < 0) return -1;
-    const SharedSplits g = decode_shared_splits(n_heads / 4, max_prefix_len, max_seqlen_k);
-    return (int64_t)(g.pre_n + g.own_n) * q_rows * n_heads * (head_dim + 2) * 4;
+    return two_range_workspace_bytes(q_rows, n_heads, head_dim, max_prefix_len, max_seqlen_k);
+}
+int64_t lmi_attn_prefix_rows_workspace_bytes(int n_rows, int n_heads, int head_dim, int prefix_len, int max_k_len) {
+    return two_range_workspace_bytes(n_rows, n_heads, head_dim, prefix_len, max_k_len);
 }
 
 static int attn_decode_shared_entry(const char* who, const void* q, const void* k_prefix, const void* v_prefix, const int* prefix_len, int max_prefix_len,
                                     const void* k, const void* v, void* out, const int* k_begin, const int* k_len, int n_seq, int max_seqlen_k, int q_rows,
                                     int n_heads, int n_kv_heads, int head_dim, int ldq, int ldkp, int ldvp, int ldk, int ldv, int ldo, float scale,
                                     void* workspace, int64_t workspace_bytes, int dtype, void* stream, int hl) {
-    if (!q || !k_prefix || !v_prefix || !prefix_len || !k || !v || !out || !k_begin || !k_len || !workspace) return fail(LMI_EINVAL, "%s: null pointer", who);
-    if (head_dim != 128) return fail(LMI_EINVAL, "%s: head_dim %d (only 128)", who, head_dim);
-    if (n_heads <= 0 || n_kv_heads <= 0 || n_heads != 4 * n_kv_heads)
-        return fail(LMI_EINVAL, "%s: needs n_heads == 4 * n_kv_heads (a workgroup's 4 waves take the query heads of one kv head), got %d / %d", who, n_heads, n_kv_heads);
-    if (n_seq < 1 || n_seq > 32) return fail(LMI_EINVAL, "%s: n_seq %d (1 .. 32: one row of a wave's 32-row tile per sequence)", who, n_seq);
-    if (max_prefix_len < 1 || max_seqlen_k < 0 || q_rows < n_seq) return fail(LMI_EINVAL, "%s: bad sizes (max_prefix_len >= 1, max_seqlen_k >= 0, q_rows >= n_seq)", who);
-    if ((ldq & 7) || (ldkp & 7) || (ldvp & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) || ldq < n_heads * head_dim || ldo < n_heads * head_dim ||
-        ldkp < n_kv_heads * head_dim || ldvp < n_kv_heads * head_dim || ldk < n_kv_heads * head_dim || ldv < n_kv_heads * head_dim)
-        return fail(LMI_EINVAL, "%s: row strides must be multiples of 8 and at least the heads' width", who);
-    if (!aligned16(q) || !aligned16(k_prefix) || !aligned16(v_prefix) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(workspace))
-        return fail(LMI_EINVAL, "%s: alignment", who);
-    if (((long)max_prefix_len * ldkp + head_dim) * 2 >= (1L << 32) || ((long)max_prefix_len * ldvp + head_dim) * 2 >= (1L << 32))
-        return fail(LMI_EINVAL, "%s: the prefix K / V rows span >= 4 GiB (max_prefix_len %d, ldkp %d, ldvp %d)", who, max_prefix_len, ldkp, ldvp);
-    if (((long)max_seqlen_k * ldk + head_dim) * 2 >= (1L << 32) || ((long)max_seqlen_k * ldv + head_dim) * 2 >= (1L << 32))
-        return fail(LMI_EINVAL, "%s: one sequence's K / V rows span >= 4 GiB (max_seqlen_k %d, ldk %d, ldv %d)", who, max_seqlen_k, ldk, ldv);
-    const int64_t need = lmi_attn_decode_shared_workspace_bytes(q_rows, n_heads, head_dim, max_prefix_len, max_seqlen_k);
-    if (workspace_bytes < need) return fail(LMI_EINVAL, "%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
-    const SharedSplits g = decode_shared_splits(n_kv_heads, max_prefix_len, max_seqlen_k);
-    AttnArgs a;
-    a.q = q; a.out = out; a.cu_q = nullptr; a.cu_k = nullptr;
-    a.out_fp8 = nullptr; a.ldo8 = 0; a.out_fp8_scale = 0.f; a.out_f32 = nullptr; a.ldo32 = 0;
-    a.out4 = nullptr; a.out4_scale = nullptr; a.ld_out4 = a.ld_out4s = 0; a.row_sel = nullptr;
-    a.ldq = ldq; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale; a.window = 0;
-    a.k_prefix = nullptr; a.v_prefix = nullptr; a.ldkp = a.ldvp = 0; a.prefix_len = 0;
-    a.check_k_extent = 0; a.gqa_pack = 1; a.n_qblocks = 1;
-    a.part_rows = q_rows;
-    a.part_o = (float*)workspace;
-    a.part_ml = a.part_o + (size_t)(g.pre_n + g.own_n) * q_rows * n_heads * head_dim;
-    AttnArgs pre = a, own = a;
-    pre.k = k_prefix; pre.v = v_prefix; pre.ldk = ldkp; pre.ldv = ldvp; pre.k_len = prefix_len; pre.prefix_len = max_prefix_len; pre.shared_rows = n_seq;
-    pre.n_splits = g.pre_n; pre.split_tiles = g.pre_tiles; pre.split_base = 0;
-    own.k = k; own.v = v; own.ldk = ldk; own.ldv = ldv; own.cu_k = k_begin; own.k_len = k_len;
-    own.n_splits = g.own_n; own.split_tiles = g.own_tiles; own.split_base = g.pre_n;
-    LMI_DISPATCH_T(dtype, (attn_decode_shared_impl<f16_t>(pre, own, n_seq, q_rows, out, ldo, stream, hl ? q_rows : 0)),
-                   (attn_decode_shared_impl<bf16_t>(pre, own, n_seq, q_rows, out, ldo, stream, hl ? q_rows : 0)));
+    if (!prefix_len) return fail(LMI_EINVAL, "%s: null pointer", who);
+    const TwoRangeWords w = {who, "", "max_prefix_len", "sequence's K / V rows span", "max_seqlen_k"};
+    const auto size_rule = [&] {
+        if (n_seq < 1 || n_seq > 32) return fail(LMI_EINVAL, "%s: n_seq %d (1 .. 32: one row of a wave's 32-row tile per sequence)", who, n_seq);
+        if (max_prefix_len < 1 || max_seqlen_k < 0 || q_rows < n_seq) return fail(LMI_EINVAL, "%s: bad sizes (max_prefix_len >= 1, max_seqlen_k >= 0, q_rows >= n_seq)", who);
+        return (int)LMI_OK;
+    };
+    AttnArgs pre, own;
+    if (int rc = two_range_args(w, size_rule, q, k_prefix, v_prefix, k, v, out, nullptr, k_begin, k_len, n_seq, q_rows, max_prefix_len, max_seqlen_k, n_heads,
+                                n_kv_heads, head_dim, ldq, ldkp, ldvp, ldk, ldv, ldo, 0, scale, workspace, workspace_bytes, pre, own))
+        return rc;
+    pre.k_len = prefix_len;                     // the prefix length lives in device memory; max_prefix_len (pre.prefix_len) bounds it
+    LMI_DISPATCH_T(dtype, (launch_attn_split_kv<f16_t>(&pre, own, n_seq, n_seq, hl ? q_rows : 0, nullptr, 0, who, stream)),
+                   (launch_attn_split_kv<bf16_t>(&pre, own, n_seq, n_seq, hl ? q_rows : 0, nullptr, 0, who, stream)));
 }
 
 int lmi_attn_decode_shared(const void* q, const void* k_prefix, const void* v_prefix, const int* prefix_len, int max_prefix_len, const void* k, const void* v,
@@ -1561,56 +1551,24 @@ int lmi_attn_decode_shared_hl(const void* q, const void* k_prefix, const void* v
                                     q_rows, n_heads, n_kv_heads, head_dim, ldq, ldkp, ldvp, ldk, ldv, ldo, scale, workspace, workspace_bytes, dtype, stream, 1);
 }
 
-int64_t lmi_attn_prefix_rows_workspace_bytes(int n_rows, int n_heads, int head_dim, int prefix_len, int max_k_len) {
-    if (n_rows < 0 || n_heads <= 0 || (n_heads & 3) || head_dim <= 0 || prefix_len < 1 || max_k_len < 0) return -1;
-    const SharedSplits g = decode_shared_splits(n_heads / 4, prefix_len, max_k_len);
-    return (int64_t)(g.pre_n + g.own_n) * n_rows * n_heads * (head_dim + 2) * 4;
-}
-
 int lmi_attn_prefix_rows(const void* q, const void* k_prefix, const void* v_prefix, int prefix_len, const void* k, const void* v, void* out, float* out_f32,
                          const int* k_begin, const int* k_len, int n_rows, int max_k_len, int n_heads, int n_kv_heads, int head_dim, int ldq, int ldkp,
                          int ldvp, int ldk, int ldv, int ldo, int ldo32, float scale, void* workspace, int64_t workspace_bytes, int dtype, void* stream) {
     const char* who = "lmi_attn_prefix_rows";
-    if (!q || !k_prefix || !v_prefix || !k || !v || !out || !k_begin || !k_len || !workspace) return fail(LMI_EINVAL, "%s: null pointer", who);
-    if (head_dim != 128) return fail(LMI_EINVAL, "%s: head_dim %d (only 128)", who, head_dim);
-    if (n_heads <= 0 || n_kv_heads <= 0 || n_heads != 4 * n_kv_heads)
-        return fail(LMI_EINVAL, "%s: needs n_heads == 4 * n_kv_heads (a workgroup's 4 waves take the query heads of one kv head), got %d / %d", who, n_heads, n_kv_heads);
-    if (n_rows < 0 || prefix_len < 1 || max_k_len < 0) return fail(LMI_EINVAL, "%s: bad sizes (n_rows >= 0, prefix_len >= 1, max_k_len >= 0)", who);
-    if ((ldq & 7) || (ldkp & 7) || (ldvp & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) || ldq < n_heads * head_dim || ldo < n_heads * head_dim ||
-        ldkp < n_kv_heads * head_dim || ldvp < n_kv_heads * head_dim || ldk < n_kv_heads * head_dim || ldv < n_kv_heads * head_dim ||
-        (out_f32 && ((ldo32 & 3) || ldo32 < n_heads * head_dim)))
-        return fail(LMI_EINVAL, "%s: row strides must be multiples of 8 (fp32 rows: 4) and at least the heads' width", who);
-    if (!aligned16(q) || !aligned16(k_prefix) || !aligned16(v_prefix) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(workspace) ||
-        (out_f32 && !aligned16(out_f32)))
-        return fail(LMI_EINVAL, "%s: alignment", who);
-    if (((long)prefix_len * ldkp + head_dim) * 2 >= (1L << 32) || ((long)prefix_len * ldvp + head_dim) * 2 >= (1L << 32))
-        return fail(LMI_EINVAL, "%s: the prefix K / V rows span >= 4 GiB (prefix_len %d, ldkp %d, ldvp %d)", who, prefix_len, ldkp, ldvp);
-    if (((long)max_k_len * ldk + head_dim) * 2 >= (1L << 32) || ((long)max_k_len * ldv + head_dim) * 2 >= (1L << 32))
-        return fail(LMI_EINVAL, "%s: one row's own K / V range spans >= 4 GiB (max_k_len %d, ldk %d, ldv %d)", who, max_k_len, ldk, ldv);
-    const int64_t need = lmi_attn_prefix_rows_workspace_bytes(n_rows, n_heads, head_dim, prefix_len, max_k_len);
-    if (workspace_bytes < need) return fail(LMI_EINVAL, "%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
-    const SharedSplits g = decode_shared_splits(n_kv_heads, prefix_len, max_k_len);
-    const long own_grid = (long)n_kv_heads * n_rows * g.own_n, items = (long)n_rows * n_heads;
+    const TwoRangeWords w = {who, " (fp32 rows: 4)", "prefix_len", "row's own K / V range spans", "max_k_len"};
+    const auto size_rule = [&] {
+        if (n_rows < 0 || prefix_len < 1 || max_k_len < 0) return fail(LMI_EINVAL, "%s: bad sizes (n_rows >= 0, prefix_len >= 1, max_k_len >= 0)", who);
+        return (int)LMI_OK;
+    };
+    AttnArgs pre, own;
+    if (int rc = two_range_args(w, size_rule, q, k_prefix, v_prefix, k, v, out, out_f32, k_begin, k_len, n_rows, n_rows, prefix_len, max_k_len, n_heads,
+                                n_kv_heads, head_dim, ldq, ldkp, ldvp, ldk, ldv, ldo, ldo32, scale, workspace, workspace_bytes, pre, own))
+        return rc;
+    const long own_grid = (long)n_kv_heads * n_rows * own.n_splits, items = (long)n_rows * n_heads;
     if (own_grid >= (1L << 31) || items >= (1L << 31)) return fail(LMI_EINVAL, "%s: n_rows %d is more than one launch grid holds", who, n_rows);
     if (n_rows == 0) return LMI_OK;
-    AttnArgs a;
-    a.q = q; a.out = out; a.cu_q = nullptr; a.cu_k = nullptr;
-    a.out_fp8 = nullptr; a.ldo8 = 0; a.out_fp8_scale = 0.f; a.out_f32 = nullptr; a.ldo32 = 0;
-    a.out4 = nullptr; a.out4_scale = nullptr; a.ld_out4 = a.ld_out4s = 0; a.row_sel = nullptr;
-    a.ldq = ldq; a.ldo = ldo; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.scale = scale; a.window = 0;
-    a.k_prefix = nullptr; a.v_prefix = nullptr; a.ldkp = a.ldvp = 0; a.prefix_len = 0;
-    a.check_k_extent = 0; a.gqa_pack = 1; a.n_qblocks = 1;
-    a.part_rows = n_rows;
-    a.part_o = (float*)workspace;
-    a.part_ml = a.part_o + (size_t)(g.pre_n + g.own_n) * n_rows * n_heads * head_dim;
-    AttnArgs pre = a, own = a;
-    pre.k = k_prefix; pre.v = v_prefix; pre.ldk = ldkp; pre.ldv = ldvp; pre.k_len = nullptr; pre.prefix_len = prefix_len; pre.shared_rows = n_rows;
-    pre.n_qblocks = (n_rows + 31) / 32;
-    pre.n_splits = g.pre_n; pre.split_tiles = g.pre_tiles; pre.split_base = 0;
-    own.k = k; own.v = v; own.ldk = ldk; own.ldv = ldv; own.cu_k = k_begin; own.k_len = k_len;
-    own.n_splits = g.own_n; own.split_tiles = g.own_tiles; own.split_base = g.pre_n;
-    LMI_DISPATCH_T(dtype, (attn_prefix_rows_impl<f16_t>(pre, own, n_rows, out, ldo, out_f32, ldo32, stream)),
-                   (attn_prefix_rows_impl<bf16_t>(pre, own, n_rows, out, ldo, out_f32, ldo32, stream)));
+    LMI_DISPATCH_T(dtype, (launch_attn_split_kv<f16_t>(&pre, own, n_rows, n_rows, 0, out_f32, ldo32, who, stream)),
+                   (launch_attn_split_kv<bf16_t>(&pre, own, n_rows, n_rows, 0, out_f32, ldo32, who, stream)));
 }
 
 static int gemm_skinny_entry(const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, int packed,
