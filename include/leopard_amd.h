@@ -583,6 +583,24 @@ int lmi_token_logprobs(const float* logits, const int64_t* rows, const int64_t* 
 int lmi_decode_logprobs(const float* logits, int B, int vocab, int ld_logits, const int64_t* tok, const int* hist_pos, int ring_len, int top_k,
                         float* lp, int* top_id, float* top_lp, void* stream);
 
+/* The logits processors of a decode step (generate(rules=...)): the launch after the head and BEFORE lmi_decode_advance / lmi_decode_sample,
+ * one 1024-thread workgroup per sequence b, rewriting the fp32 row logits[b] (columns [0, vocab)) in place, in HF's processor order.  A row
+ * with live[b] == 0 (live nullable) is frozen: nothing is read, written or advanced.  Otherwise:
+ *   append    tok non-null and seq_len[b] < seq_cap: seq[b][seq_len[b]] = tok[b], seq_len[b] += 1 (the token this step consumes).  L = seq_len[b].
+ *   penalty   penalty[b] != 1: every id of seq[b][0 .. L) in [0, vocab) is rewritten once, however often it occurs: l < 0 ? l * p : l / p
+ *             (one fp32 multiply or one IEEE fp32 divide; RepetitionPenaltyLogitsProcessor).
+ *   n-gram    n = ngram[b] > 0, L + 1 >= n: every start i in [0, L - n + 1) whose n - 1 ids equal the last n - 1 ids of the sequence sets
+ *             logits[seq[i + n - 1]] = -inf (NoRepeatNGramLogitsProcessor; n = 1 bans every id seen).  Ids outside [0, vocab) are compared
+ *             and never written.  -inf wins over a penalised value.
+ *   minimum   min_left[b] > 0: logits[eos[j]] = -inf for every eos id in [0, vocab) (entries < 0 unused), then min_left[b] -= 1.
+ * seq int32 [B, seq_cap], seq_len / ngram / min_left int32 [B], penalty fp32 [B] (> 0), tok int64 [B], eos int64 [n_eos].  The result does
+ * not depend on thread order or on B.  No allocation, no host synchronisation, graph-capturable.  LMI_EINVAL: null pointer (tok, live and —
+ * with n_eos == 0 — eos excepted), ld_logits < vocab, seq_cap < 1, vocab > LMI_RULES_MAX_VOCAB (the bitmap of seen ids is one bit per id in
+ * 32 KB of LDS).  leopard_amd/csrc/decode_rules.h. */
+#define LMI_RULES_MAX_VOCAB 262144
+int lmi_decode_rules(float* logits, int B, int vocab, int ld_logits, const int64_t* tok, const int* live, int* seq, int* seq_len, int seq_cap,
+                     const float* penalty, const int* ngram, int* min_left, const int64_t* eos, int n_eos, void* stream);
+
 /* ---- multi-GPU: RCCL collectives over xGMI (SURVEY.md 8(b) "lmi_allgather / lmi_allreduce wrappers over RCCL communicators
  * ... created by lmi_comm_init(rank, nranks, unique_id) and freed by lmi_comm_destroy", 8(e)).  The reference's evaluation is one
  * process per GPU with no collective (run_eval_llava_siglip_multiimg.sh:9-11); its training side states the exchange pattern

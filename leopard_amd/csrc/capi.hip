@@ -19,6 +19,7 @@
 #include "sample.h"
 #include "logprob.h"
 #include "decode_logprob.h"
+#include "decode_rules.h"
 
 using namespace lmi;
 
@@ -1844,6 +1845,23 @@ int lmi_decode_logprobs(const float* logits, int B, int vocab, int ld_logits, co
     a.lp = lp; a.top_id = top_id; a.top_lp = top_lp;
     LMI_LAUNCH(decode_logprobs_kernel, dim3(B), dim3(kLogprobThreads), 0, stream, a);
     return check_launch("lmi_decode_logprobs");
+}
+
+int lmi_decode_rules(float* logits, int B, int vocab, int ld_logits, const int64_t* tok, const int* live, int* seq, int* seq_len, int seq_cap,
+                     const float* penalty, const int* ngram, int* min_left, const int64_t* eos, int n_eos, void* stream) {
+    static_assert(kRulesMaxVocab == LMI_RULES_MAX_VOCAB, "the kernel's bitmap is the header's constant");
+    if (!logits || !seq || !seq_len || !penalty || !ngram || !min_left) return fail(LMI_EINVAL, "lmi_decode_rules: null pointer");
+    if (B < 0 || vocab <= 0 || ld_logits < vocab || seq_cap < 1 || n_eos < 0 || (n_eos && !eos))
+        return fail(LMI_EINVAL, "lmi_decode_rules: bad argument (B=%d vocab=%d ld_logits=%d seq_cap=%d n_eos=%d; ld_logits >= vocab, seq_cap >= 1)", B,
+                    vocab, ld_logits, seq_cap, n_eos);
+    if (vocab > LMI_RULES_MAX_VOCAB)
+        return fail(LMI_EINVAL, "lmi_decode_rules: vocab %d exceeds %d (one bit per id in 32 KB of LDS)", vocab, LMI_RULES_MAX_VOCAB);
+    if (B == 0) return LMI_OK;
+    DecodeRulesArgs a;
+    a.logits = logits; a.tok = tok; a.live = live; a.seq = seq; a.seq_len = seq_len; a.penalty = penalty; a.ngram = ngram; a.min_left = min_left;
+    a.eos = eos; a.vocab = vocab; a.ld = ld_logits; a.seq_cap = seq_cap; a.n_eos = n_eos;
+    LMI_LAUNCH(decode_rules_kernel, dim3(B), dim3(kRulesThreads), 0, stream, a);
+    return check_launch("lmi_decode_rules");
 }
 
 int lmi_gemv_rmsnorm(const void* W, const float* x, const float* norm_weight, float eps, void* out, int N, int K, int ldw,

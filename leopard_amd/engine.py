@@ -181,6 +181,38 @@ class SamplingParams:
         return f"sample(temperature={self.temperature:g}, top_k={int(self.top_k)}, top_p={self.top_p:g})"
 
 
+@dataclass(frozen=True)
+class LogitsRules:
+    """Logits processors of a generation call (lmi_decode_rules, csrc/decode_rules.h), applied inside the decode step before the choice, in
+    HF's order: ``repetition_penalty`` (1.0 = off) over every id of the prompt and of the tokens generated so far, ``no_repeat_ngram_size``
+    (0 = off) over the same ids, ``min_new_tokens`` (0 = off): the call's eos ids cannot be chosen before that many new tokens exist."""
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    min_new_tokens: int = 0
+
+    def __post_init__(self):
+        if not float(self.repetition_penalty) > 0:
+            raise ValueError(f"repetition_penalty must be > 0, got {self.repetition_penalty}")
+        if int(self.no_repeat_ngram_size) < 0:
+            raise ValueError(f"no_repeat_ngram_size must be >= 0, got {self.no_repeat_ngram_size}")
+        if int(self.min_new_tokens) < 0:
+            raise ValueError(f"min_new_tokens must be >= 0, got {self.min_new_tokens}")
+
+    @property
+    def active(self) -> bool:
+        return float(self.repetition_penalty) != 1.0 or int(self.no_repeat_ngram_size) > 0 or int(self.min_new_tokens) > 0
+
+    def describe(self) -> str:
+        parts = []
+        if float(self.repetition_penalty) != 1.0:
+            parts.append(f"repetition_penalty={float(self.repetition_penalty):g}")
+        if int(self.no_repeat_ngram_size) > 0:
+            parts.append(f"no_repeat_ngram_size={int(self.no_repeat_ngram_size)}")
+        if int(self.min_new_tokens) > 0:
+            parts.append(f"min_new_tokens={int(self.min_new_tokens)}")
+        return " + ".join(parts)
+
+
 @contextlib.contextmanager
 def _capture_safe():
     """Hold off Python's cyclic garbage collector while a HIP graph is captured.  A collection that starts inside the capture runs the
@@ -239,8 +271,19 @@ class DecodeState:
     top_id: Optional[torch.Tensor] = None
     top_lp: Optional[torch.Tensor] = None
     logprobs: Optional[int] = None               # k of the running call: the step also launches lmi_decode_logprobs
+    # generate(rules=...): the device side of lmi_decode_rules — per slot the ids seen so far (the prompt as the caller passed it, then one
+    # id per step, appended by the kernel), its parameters and the steps eos stays banned; the eos ids of the running call.  4 bytes x
+    # (prefix_capacity + capacity) per slot.  Allocated by the first call with ``rules`` (_set_rules): a state that never sees one holds
+    # what it held before.  The parameters are device values: other values never capture again
+    rules: bool = False                          # the running call has rules: the step launches lmi_decode_rules before the choice
+    seq: Optional[torch.Tensor] = None           # int32 [B, prefix_capacity + capacity]
+    seq_len: Optional[torch.Tensor] = None       # int32 [B]
+    rule_pen: Optional[torch.Tensor] = None      # fp32 [B]
+    rule_ngram: Optional[torch.Tensor] = None    # int32 [B]
+    rule_min_left: Optional[torch.Tensor] = None  # int32 [B]
+    rule_eos: Optional[torch.Tensor] = None      # int64 [MAX_EOS], -1 = unused
     # the captured steps (LeopardEngine._run_step), keyed by (sampling, with logprobs): greedy / sampled, each without and with the logprobs
-    # launch — the latter two with top_k = lp_k
+    # launch — the latter two with top_k = lp_k — and by (sampling, False, True) for the steps with the rules launch
     graphs: dict = field(default_factory=dict)
     lp_k: Optional[int] = None                   # the top_k the two logprobs graphs were captured with (another k captures them again)
     graph_failed: bool = False                   # tensor parallel: the capture failed once, the step runs eagerly (_decode_run)
@@ -1736,14 +1779,88 @@ class LeopardEngine:
 
     def _choose(self, st, logits, **kw) -> None:
         """The tail of a decode step: lmi_decode_advance (greedy) or lmi_decode_sample (st.sampling) — the only difference between the two
-        captured steps."""
+        captured steps — after lmi_decode_rules when the call has rules (HF's order: processors, then suppress list, then warpers)."""
         V = self.cfg.text_config.vocab_size
+        if st.rules:                                                  # generate(rules=...): one more launch, before the choice (it rewrites the rows)
+            self.ops.decode_rules(logits, V, st.seq, st.seq_len, st.rule_pen, st.rule_ngram, st.rule_min_left, tok=st.tok, live=kw.get("live"),
+                                  eos=st.rule_eos)
         if st.sampling:
             self.ops.decode_sample(logits, V, st.temp, st.topk, st.topp, st.seed, st.step, st.tok, st.pos, suppress=self.suppress_tokens, **kw)
         else:
             self.ops.decode_advance(logits, V, st.tok, st.pos, suppress=self.suppress_tokens, **kw)
         if st.logprobs is not None:                                   # generate(logprobs=k): one more launch, after the choice (it reads st.tok)
             self.ops.decode_logprobs(logits, V, st.tok, st.logprobs, st.lp, st.top_id, st.top_lp, hist_pos=kw.get("hist_pos"))
+
+    # ---- generate(rules=...): the host side ----
+    def _rules_arg(self, what: str, rules: Optional[LogitsRules], logprobs: Optional[int], eos_token_id) -> Optional[LogitsRules]:
+        """Validate ``rules`` before anything is launched: None when absent or with everything off."""
+        if rules is None:
+            return None
+        if not isinstance(rules, LogitsRules):
+            raise TypeError(f"{what}: rules must be a LogitsRules, got {type(rules).__name__}")
+        if not rules.active:
+            return None
+        if logprobs is not None:
+            raise NotImplementedError(f"{what}: rules with logprobs is not supported (the logprob rings promise values of the RAW logits row, "
+                                      "and lmi_decode_rules rewrites the row in place before the choice)")
+        if self.tp_size > 1:
+            raise NotImplementedError(f"{what}: rules are not supported on tensor-parallel engines (the rules launch and its per-slot state belong "
+                                      "to the single-rank decode step)")
+        if int(rules.min_new_tokens) > 0 and len(set(int(e) for e in eos_token_id)) > self.MAX_EOS:
+            raise NotImplementedError(f"{what}: min_new_tokens with more than {self.MAX_EOS} eos ids is not supported (the device holds "
+                                      f"{self.MAX_EOS})")
+        V = self.cfg.text_config.vocab_size
+        if V > self.ops.RULES_MAX_VOCAB:
+            raise NotImplementedError(f"{what}: rules need a vocabulary of at most {self.ops.RULES_MAX_VOCAB} ids (this model: {V})")
+        return rules
+
+    def _rule_eos(self, rules: LogitsRules, eos) -> torch.Tensor:
+        """The eos ids the minimum-length rule bans, int64 [MAX_EOS] on the host (-1 = unused; all unused without that rule)."""
+        ids = sorted(set(int(e) for e in eos)) if int(rules.min_new_tokens) > 0 else []
+        return torch.tensor(ids + [-1] * (self.MAX_EOS - len(ids)), dtype=torch.int64)
+
+    def _set_rules(self, st, rules: Optional[LogitsRules], eos=()) -> None:
+        """The state runs the step with (or without) the rules launch; the first call with rules allocates their buffers."""
+        st.rules = rules is not None
+        if rules is None:
+            return
+        if st.seq is None:
+            dev, B = self.device, st.B
+            st.seq = torch.zeros(B, st.prefix_capacity + st.capacity, dtype=torch.int32, device=dev)
+            st.seq_len = torch.zeros(B, dtype=torch.int32, device=dev)
+            st.rule_pen = torch.ones(B, dtype=torch.float32, device=dev)
+            st.rule_ngram = torch.zeros(B, dtype=torch.int32, device=dev)
+            st.rule_min_left = torch.zeros(B, dtype=torch.int32, device=dev)
+            st.rule_eos = torch.full((self.MAX_EOS,), -1, dtype=torch.int64, device=dev)
+        st.rule_eos.copy_(self._rule_eos(rules, eos))
+
+    def _fill_rules(self, st, j: int, prompt: Sequence[int], rules: LogitsRules) -> None:
+        """Slot j starts a request under ``rules``: its ids so far are the prompt's (the first token is appended by step 1's kernel, from
+        st.tok), and eos stays banned for min_new_tokens - 1 more steps (the first token was chosen under the rule already)."""
+        n = len(prompt)
+        if n >= st.seq.shape[1]:
+            raise ValueError(f"rules: a prompt of {n} ids does not fit the {st.seq.shape[1]} ids a decode slot holds")
+        st.seq[j, :n].copy_(torch.tensor(list(prompt), dtype=torch.int32))
+        ints = torch.tensor([n, int(rules.no_repeat_ngram_size), max(int(rules.min_new_tokens) - 1, 0)], dtype=torch.int32)
+        st.seq_len[j:j + 1].copy_(ints[0:1]); st.rule_ngram[j:j + 1].copy_(ints[1:2]); st.rule_min_left[j:j + 1].copy_(ints[2:3])
+        st.rule_pen[j:j + 1].copy_(torch.tensor([float(rules.repetition_penalty)], dtype=torch.float32))
+
+    def first_rules(self, logits: torch.Tensor, prompts: Sequence[Sequence[int]], rules: LogitsRules, eos) -> torch.Tensor:
+        """The prefill / extend logits rows ([n, >= vocab] or [vocab]) after the rules, for the FIRST token of each request: the same kernel
+        as inside the step, run eagerly on a COPY of the rows (the caller's logits are never modified), nothing appended (the ids seen are
+        the prompt's), eos banned when min_new_tokens > 0."""
+        rows = logits.reshape(-1, logits.shape[-1]).to(torch.float32).clone().contiguous()
+        n, dev = rows.shape[0], rows.device
+        assert len(prompts) == n
+        seq = torch.zeros(n, max(max(len(p) for p in prompts), 1), dtype=torch.int32)
+        for j, p in enumerate(prompts):
+            seq[j, :len(p)] = torch.tensor(list(p), dtype=torch.int32)
+        full = lambda v, dt: torch.full((n,), v, dtype=dt).to(dev)
+        self.ops.decode_rules(rows, min(self.cfg.text_config.vocab_size, rows.shape[1]), seq.to(dev),
+                              torch.tensor([len(p) for p in prompts], dtype=torch.int32).to(dev), full(float(rules.repetition_penalty), torch.float32),
+                              full(int(rules.no_repeat_ngram_size), torch.int32), full(int(rules.min_new_tokens), torch.int32),
+                              eos=self._rule_eos(rules, eos).to(dev))
+        return rows
 
     # ---- generate(logprobs=k): the host side ----
     def _logprobs_arg(self, what: str, logprobs: Optional[int]) -> Optional[int]:
@@ -1767,7 +1884,7 @@ class LeopardEngine:
             st.lp, st.top_id = st.lp_buf[:n].view(torch.float32).view(ring, st.B), st.lp_buf[n:n * (1 + K)].view(ring, st.B, K)
             st.top_lp = st.lp_buf[n * (1 + K):].view(torch.float32).view(ring, st.B, K)
         if k is not None and st.lp_k != k:                            # top_k is a launch argument: the captured logprobs steps hold one value
-            st.graphs.pop((False, True), None); st.graphs.pop((True, True), None)
+            st.graphs.pop((False, True), None); st.graphs.pop((True, True), None)      # (the steps with rules never hold the logprobs launch)
             st.lp_k = k
 
     def _rings_to_host(self, st):
@@ -1806,11 +1923,15 @@ class LeopardEngine:
         res = [r.result(len(t) - int(p)) for r, t, p in zip(lpr, toks, n_prompt)]
         return GenerateOutput(seqs, [r[0] for r in res], [r[1] for r in res], [r[2] for r in res])
 
-    def _first_tokens(self, logits: torch.Tensor, params: Optional[Sequence["SamplingParams"]], k: Optional[int]):
+    def _first_tokens(self, logits: torch.Tensor, params: Optional[Sequence["SamplingParams"]], k: Optional[int],
+                      rules: Optional[LogitsRules] = None, prompts: Optional[Sequence[Sequence[int]]] = None, eos=()):
         """The first token of each of n requests from its prefill / extend logits row ([n, >= vocab] or [vocab]): greedy (``params`` None) or
-        drawn with its SamplingParams at step 0, then — ``logprobs`` = k — one eager logprobs launch for all of them.  Returns (first
+        drawn with its SamplingParams at step 0, then — ``logprobs`` = k — one eager logprobs launch for all of them.  With ``rules`` the
+        choice is made from a copy of the rows that lmi_decode_rules has rewritten over ``prompts`` (first_rules).  Returns (first
         [n], the requests' _LogprobRows holding that first row, or None)."""
         rows = logits.reshape(-1, logits.shape[-1])
+        if rules is not None:
+            rows = self.first_rules(rows, prompts, rules, eos)
         first = [self.first_token(r) for r in rows] if params is None else self.sample_first(rows, params)
         if k is None:
             return first, None
@@ -1837,14 +1958,16 @@ class LeopardEngine:
 
     def _run_step(self, st, body, restore: tuple, capturable: bool = True) -> None:
         """One decode step of ``st``.  ``body`` runs eagerly on the emulator, off a device, with graphs off or when the step is not
-        ``capturable``; otherwise the captured step of (st.sampling, with logprobs) is replayed — warmed up and captured on its first use
-        (two Python runs of ``body``), after each of which the device state the step advances (``restore``, and the logprob rings) is put back."""
+        ``capturable``; otherwise the captured step of (st.sampling, with logprobs[, with rules]) is replayed — warmed up and captured on its
+        first use (two Python runs of ``body``), after each of which the device state the step advances (``restore``, the logprob rings, the
+        rules' sequence length and eos countdown; the id the rules launch appended lands in the same cell again) is put back."""
         if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs or not capturable:
             body()
             return
-        key = (st.sampling, st.logprobs is not None)
+        key = (st.sampling, st.logprobs is not None) + ((True,) if st.rules else ())
         if key not in st.graphs:
-            st.graphs[key], _ = self._capture_graph(body, restore + (() if st.logprobs is None else (st.lp_buf,)))
+            st.graphs[key], _ = self._capture_graph(body, restore + (() if st.logprobs is None else (st.lp_buf,)) +
+                                                    ((st.seq_len, st.rule_min_left) if st.rules else ()))
         st.graphs[key].replay()
 
     def _decode_run(self, st, cache: KVCache):
@@ -1898,7 +2021,7 @@ class LeopardEngine:
     def decode_step(self, token_id: int, cache: KVCache) -> torch.Tensor:
         """Append one token: returns its logits [vocab] (fp32, a view of a static buffer) and advances the cache."""
         st = self._decode_state(cache)
-        st.sampling, st.logprobs = False, None
+        st.sampling, st.logprobs, st.rules = False, None, False      # raw logits: never rules
         self._decode_seed(st, cache, token_id)
         self._decode_run(st, cache)
         cache.length += 1
@@ -1923,7 +2046,8 @@ class LeopardEngine:
         return int(logits_last.argmax())
 
     def _greedy_loop(self, prompt_ids: List[int], first: int, cache: KVCache, max_new_tokens: int, eos,
-                     sampling: Optional[SamplingParams] = None, lpr: Optional[_LogprobRows] = None) -> List[int]:
+                     sampling: Optional[SamplingParams] = None, lpr: Optional[_LogprobRows] = None,
+                     rules: Optional[LogitsRules] = None) -> List[int]:
         """EVAL:448-452 after the prefill: greedy tokens until eos / max_new_tokens; one captured decode step per token.  With ``sampling``
         the step draws instead (the sampled graph; ``first`` was drawn at step 0).  ``lpr`` (generate(logprobs=k)): the step also writes the
         token's logprob row, read with one more small copy next to the token's."""
@@ -1931,6 +2055,9 @@ class LeopardEngine:
         st = self._decode_state(cache)
         st.sampling = sampling is not None
         self._set_logprobs(st, None if lpr is None else lpr.k)
+        self._set_rules(st, rules, eos)
+        if rules is not None:
+            self._fill_rules(st, 0, prompt_ids, rules)
         if sampling is not None:
             self._set_sampling(st, 0, sampling)
         self._decode_seed(st, cache, nxt)
@@ -1947,7 +2074,7 @@ class LeopardEngine:
         return out
 
     def _continue_single(self, prompt: List[int], first: int, pieces, max_new_tokens: int, eos, sampling: Optional[SamplingParams],
-                         lpr: Optional[_LogprobRows]) -> List[int]:
+                         lpr: Optional[_LogprobRows], rules: Optional[LogitsRules] = None) -> List[int]:
         """One request whose K / V rows are ``pieces`` (_load_rows) continued on the engine's ONE generation cache and its captured batch-1
         step: a chunk of one suffix, or the requests of a call one after another where the shape has no batched decode (toy configurations
         the skinny-M kernels do not cover)."""
@@ -1955,23 +2082,27 @@ class LeopardEngine:
         cache = self._generation_cache(S + max_new_tokens)
         self._load_rows(pieces, cache.k, cache.v, 0)
         cache.length = S
-        return self._greedy_loop(prompt, first, cache, max_new_tokens, eos, sampling, lpr)
+        return self._greedy_loop(prompt, first, cache, max_new_tokens, eos, sampling, lpr, rules)
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, tiles: Optional[torch.Tensor], max_new_tokens: int = 128,
                  eos_token_id: Sequence[int] = (128001, 128009), sampling: Optional[SamplingParams] = None,
-                 logprobs: Optional[int] = None):
+                 logprobs: Optional[int] = None, rules: Optional[LogitsRules] = None):
         """Greedy generation (EVAL:448-452), or sampled with ``sampling``: returns LongTensor [1, S_in + T] on the input device.
         ``logprobs`` = k in 0 .. 8: returns a ``GenerateOutput`` — that tensor as ``sequences`` plus, for each of the T generated tokens, its
-        log-probability and the k most likely tokens of its step (lmi_decode_logprobs inside the captured step)."""
+        log-probability and the k most likely tokens of its step (lmi_decode_logprobs inside the captured step).
+        ``rules``: repetition penalty / no-repeat n-gram ban / min_new_tokens over the ids of ``input_ids`` (as passed: an image placeholder
+        counts as its id) and the generated tokens, applied inside the step before the choice (lmi_decode_rules), the first token included.
+        Not with ``logprobs``, not on tensor-parallel engines (NotImplementedError, before anything is launched)."""
         k = self._logprobs_arg("generate", logprobs)
+        rules = self._rules_arg("generate", rules, k, eos_token_id)
         ids = input_ids.reshape(1, -1)
         S = self.merged_len(ids)
         cache = self._generation_cache((self.tp_padded_len(S) if self.tp_size > 1 else S) + max_new_tokens)
         res = self.prefill(ids, tiles, cache=cache)
-        first, lpr = self._first_tokens(res.logits_last, None if sampling is None else [sampling], k)
-        out = self._greedy_loop([int(t) for t in ids.reshape(-1).tolist()], first[0], cache, max_new_tokens,
-                                set(int(e) for e in eos_token_id), sampling, lpr and lpr[0])
+        prompt, eos = [int(t) for t in ids.reshape(-1).tolist()], set(int(e) for e in eos_token_id)
+        first, lpr = self._first_tokens(res.logits_last, None if sampling is None else [sampling], k, rules, [prompt], eos)
+        out = self._greedy_loop(prompt, first[0], cache, max_new_tokens, eos, sampling, lpr and lpr[0], rules)
         return self._outputs([out], [input_ids], lpr, [ids.numel()], one=True)
 
     # ------------------------------------------------------------------------------------------------
@@ -2172,7 +2303,7 @@ class LeopardEngine:
 
     def _greedy_loop_batch(self, st, prompts: List[List[int]], first: List[int], seq_lens: List[int], max_new_tokens: int, eos,
                            sampling: Optional[Sequence[SamplingParams]] = None, own_lens: Optional[List[int]] = None,
-                           lpr: Optional[Sequence[_LogprobRows]] = None) -> List[List[int]]:
+                           lpr: Optional[Sequence[_LogprobRows]] = None, rules: Optional[LogitsRules] = None) -> List[List[int]]:
         """EVAL:448-452 for B sequences at once: every sequence follows exactly the batch-1 rule (emit, stop at eos / max_new_tokens);
         finished sequences keep riding along in the batch (their slots are private) and are ignored.  ``own_lens`` (a shared-prefix state):
         the rows each slot holds — the key count starts there, the position at seq_lens.  ``lpr`` (logprobs=k): the steps also fill the
@@ -2188,6 +2319,10 @@ class LeopardEngine:
         st.live.fill_(1); st.budget.fill_(1 << 30); st.eos.fill_(-1); st.hist_pos.zero_()      # the host applies the stop rule here
         st.sampling = sampling is not None
         self._set_logprobs(st, None if lpr is None else lpr[0].k)
+        self._set_rules(st, rules, eos)
+        if rules is not None:
+            for j, p in enumerate(prompts):
+                self._fill_rules(st, j, p, rules)
         for j, sp in enumerate(sampling or ()):
             self._set_sampling(st, j, sp)
         undrained = 0                                                 # steps whose ring slots 0 .. undrained - 1 the host has not read yet
@@ -2229,7 +2364,7 @@ class LeopardEngine:
     @torch.no_grad()
     def generate_stream(self, samples: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8, max_new_tokens: int = 128,
                         eos_token_id: Sequence[int] = (128001, 128009), stats: Optional[dict] = None,
-                        sampling: Optional[SamplingParams] = None, logprobs: Optional[int] = None):
+                        sampling: Optional[SamplingParams] = None, logprobs: Optional[int] = None, rules: Optional[LogitsRules] = None):
         """CONTINUOUS batching (the reference loop EVAL:381-452 is one generate() per record): ``batch_size`` decode slots,
         ONE captured step per token for all of them, and a slot that finishes (eos / max_new_tokens) is handed to the next pending sample
         — prefill of the newcomer, its K / V rows copied into the slot of the pooled cache, five small device writes — without
@@ -2241,14 +2376,17 @@ class LeopardEngine:
         ``stats`` (optional dict) receives steps / slot-steps / live slot-steps for occupancy accounting.
         ``sampling``: sampled decoding; request i draws with ``sampling.for_request(i)``, so its tokens do not depend on ``batch_size``.
         ``logprobs`` = k in 0 .. 8: returns a ``GenerateOutput`` (``sequences`` = that list); the logprob rings are read once per window, with
-        the token table."""
+        the token table.  ``rules``: as ``generate``, one value for every request of the call; a slot's ids and countdown are set when it
+        admits a request."""
         k = self._logprobs_arg("generate_stream", logprobs)
+        rules = self._rules_arg("generate_stream", rules, k, eos_token_id)
         assert self.tp_size == 1, "batched generation is a single-rank feature (replicas scale it out)"
         B = max(1, min(int(batch_size), self.MAX_DECODE_BATCH, len(samples)))
         eos = [int(e) for e in eos_token_id]
         req = (lambda i: None) if sampling is None else sampling.for_request
         if B == 1 or not self._batch_decode_supported() or len(eos) > self.MAX_EOS:
-            one = [self.generate(ids, t() if callable(t) else t, max_new_tokens, eos, sampling=req(i), logprobs=k) for i, (ids, t) in enumerate(samples)]
+            one = [self.generate(ids, t() if callable(t) else t, max_new_tokens, eos, sampling=req(i), logprobs=k, rules=rules)
+                   for i, (ids, t) in enumerate(samples)]
             return one if k is None else GenerateOutput.join(one)
         need = max(self.merged_len(ids) for ids, _ in samples) + max_new_tokens
         st = self._batch_state(B, need)
@@ -2258,6 +2396,7 @@ class LeopardEngine:
         st.live.zero_(); st.budget.zero_(); st.pos.zero_(); st.k_len.fill_(1); st.tok.zero_(); st.hist_pos.zero_()
         st.sampling = sampling is not None
         self._set_logprobs(st, k)
+        self._set_rules(st, rules, eos)
         lpr = None if k is None else [None] * len(samples)          # a request's rows start with its first token's (admit)
         eos_set = set(eos)
         outs: List[Optional[List[int]]] = [None] * len(samples)
@@ -2280,8 +2419,9 @@ class LeopardEngine:
                     scratch = self._stream_cache = KVCache(self.cfg, (S + 1023) // 1024 * 1024, self.dtype, self.device)
                 scratch.length = 0
                 res = self.prefill(ids.reshape(1, -1), tiles, cache=scratch)
-                (first,), rows = self._first_tokens(res.logits_last, None if sampling is None else [req(i)], k)
-                outs[i] = [int(t) for t in ids.reshape(-1).tolist()] + [first]
+                prompt = [int(t) for t in ids.reshape(-1).tolist()]
+                (first,), rows = self._first_tokens(res.logits_last, None if sampling is None else [req(i)], k, rules, [prompt], eos_set)
+                outs[i] = prompt + [first]
                 if lpr is not None:
                     lpr[i] = rows[0]
                 if first in eos_set or max_new_tokens <= 1:
@@ -2295,6 +2435,8 @@ class LeopardEngine:
                 st.live[j:j + 1].fill_(1)
                 if sampling is not None:
                     self._set_sampling(st, j, req(i))
+                if rules is not None:
+                    self._fill_rules(st, j, prompt, rules)
                 slot_sample[j], h_budget[j] = i, max_new_tokens - 1
                 return True
             return False
@@ -2334,7 +2476,7 @@ class LeopardEngine:
     @torch.no_grad()
     def generate_batch(self, samples: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], max_new_tokens: int = 128,
                        eos_token_id: Sequence[int] = (128001, 128009), sampling: Optional[SamplingParams] = None,
-                       _first_request: int = 0, logprobs: Optional[int] = None):
+                       _first_request: int = 0, logprobs: Optional[int] = None, rules: Optional[LogitsRules] = None):
         """Several samples per call (batching with per-sample cu_seqlens instead of one sample per generate()):
         ONE packed prefill — all ViT inputs through the tower together, all merged sequences in one varlen causal pass that also
         writes every sample's K/V into a packed cache — then each sample's K/V rows move to its slot of the pooled decode cache (a
@@ -2344,27 +2486,29 @@ class LeopardEngine:
         norms instead of the batch-1 FMA chains, so a greedy choice can differ where the top two logits are within the 16-bit noise (the GPU
         tests assert equality and, where it fails, exactly such a near tie).
         ``sampling``: sampled decoding, request i with ``sampling.for_request(i)`` (as generate_stream).
-        ``logprobs`` = k in 0 .. 8: returns a ``GenerateOutput`` (``sequences`` = that list); the rings are drained once per HIST steps."""
+        ``logprobs`` = k in 0 .. 8: returns a ``GenerateOutput`` (``sequences`` = that list); the rings are drained once per HIST steps.
+        ``rules``: as ``generate``, one value for every request of the call."""
         k = self._logprobs_arg("generate_batch", logprobs)
+        rules = self._rules_arg("generate_batch", rules, k, eos_token_id)
         assert self.tp_size == 1, "batched generation is a single-rank feature (replicas scale it out)"
         if len(samples) > self.MAX_DECODE_BATCH:
-            outs = [self.generate_batch(samples[i:i + self.MAX_DECODE_BATCH], max_new_tokens, eos_token_id, sampling, _first_request + i, k)
+            outs = [self.generate_batch(samples[i:i + self.MAX_DECODE_BATCH], max_new_tokens, eos_token_id, sampling, _first_request + i, k, rules)
                     for i in range(0, len(samples), self.MAX_DECODE_BATCH)]
             return [o for part in outs for o in part] if k is None else GenerateOutput.join(outs)
         req = (lambda i: None) if sampling is None else (lambda i: sampling.for_request(_first_request + i))
         if len(samples) == 1:
             ids, t = samples[0]
-            one = self.generate(ids, t, max_new_tokens, eos_token_id, sampling=req(0), logprobs=k)
+            one = self.generate(ids, t, max_new_tokens, eos_token_id, sampling=req(0), logprobs=k, rules=rules)
             return [one] if k is None else GenerateOutput.join([one])
         x, seq_lens = self._pack_requests(samples)
         packed = KVCache(self.cfg, sum(seq_lens), self.dtype, self.device)
         last, _ = self.llm_prefill(x, seq_lens, cache=packed)
-        first, lpr = self._first_tokens(last, None if sampling is None else [req(j) for j in range(last.shape[0])], k)
         prompts = [[int(t) for t in ids.reshape(-1).tolist()] for ids, _ in samples]
         eos = set(int(e) for e in eos_token_id)
+        first, lpr = self._first_tokens(last, None if sampling is None else [req(j) for j in range(last.shape[0])], k, rules, prompts, eos)
         offs = [0] + [int(c) for c in np.cumsum(seq_lens)]
         if not self._batch_decode_supported():
-            outs = [self._continue_single(prompts[j], first[j], [(packed, offs[j], S)], max_new_tokens, eos, req(j), lpr and lpr[j])
+            outs = [self._continue_single(prompts[j], first[j], [(packed, offs[j], S)], max_new_tokens, eos, req(j), lpr and lpr[j], rules)
                     for j, S in enumerate(seq_lens)]
         else:
             st = self._batch_state(len(samples), max(seq_lens) + max_new_tokens)
@@ -2372,7 +2516,7 @@ class LeopardEngine:
                 self._load_rows([(packed, offs[j], S)], st.k, st.v, j * st.capacity)
             del packed
             outs = self._greedy_loop_batch(st, prompts, first, seq_lens, max_new_tokens, eos,
-                                           None if sampling is None else [req(j) for j in range(len(samples))], lpr=lpr)
+                                           None if sampling is None else [req(j) for j in range(len(samples))], lpr=lpr, rules=rules)
         return self._outputs(outs, [ids for ids, _ in samples], lpr, [len(p) for p in prompts])
 
     # ------------------------------------------------------------------------------------------------
@@ -2656,7 +2800,7 @@ class LeopardEngine:
     def generate_shared(self, prefix_ids: torch.Tensor, tiles: Optional[torch.Tensor], suffixes: Sequence[torch.Tensor],
                         max_new_tokens: int = 128, eos_token_id: Sequence[int] = (128001, 128009),
                         sampling: Optional[SamplingParams] = None, prefix: Optional[KVCache] = None, decode: str = "copy",
-                        logprobs: Optional[int] = None):
+                        logprobs: Optional[int] = None, rules: Optional[LogitsRules] = None):
         """N prompts that share their head — ``prefix_ids`` with all the images (``tiles``) — and differ in a text suffix (the question):
         ONE prefill of the prefix (the vision tower runs once) into a cache of exactly P rows, ONE ``extend`` of the N suffixes, then request
         j's rows — the P prefix rows and its own s_j — are copied into decode slot j and the batch continues through the unchanged batched
@@ -2673,8 +2817,10 @@ class LeopardEngine:
         ``prefix``: a cache that a ``prefill(prefix_ids, tiles, cache=prefix)`` has already filled — the prefill is skipped (``tiles`` is not
         read) and, as with ``extend``, the cache is left untouched.
         ``logprobs`` = k in 0 .. 8: returns a ``GenerateOutput`` (``sequences`` = that list), in both ``decode`` modes; a request's T counts
-        the tokens after its suffix."""
+        the tokens after its suffix.
+        ``rules``: as ``generate``, in both ``decode`` modes and on the batch-1 paths; a request's ids are ``prefix_ids`` + its suffix."""
         k = self._logprobs_arg("generate_shared", logprobs)
+        rules = self._rules_arg("generate_shared", rules, k, eos_token_id)
         if decode not in ("copy", "shared"):
             raise ValueError(f"generate_shared: decode must be 'copy' or 'shared', got {decode!r}")
         self._continuation_guard("generate_shared")
@@ -2701,17 +2847,17 @@ class LeopardEngine:
             stepping = max_new_tokens > 1
             kv = KVCache(self.cfg, sum(lens), self.dtype, self.device) if stepping else None
             res = self.extend(prefix, chunk, kv_out=kv)
-            first, lpr = self._first_tokens(res.logits, None if sampling is None else req, k)
+            prompts = [head + [int(t) for t in ids.reshape(-1).tolist()] for ids in chunk]
+            first, lpr = self._first_tokens(res.logits, None if sampling is None else req, k, rules, prompts, eos)
             if lpr is not None:
                 rows_all += lpr
-            prompts = [head + [int(t) for t in ids.reshape(-1).tolist()] for ids in chunk]
             offs = [0] + [int(c) for c in np.cumsum(lens)]
             own = [[(kv, offs[j], s)] for j, s in enumerate(lens)]       # a request's own rows ...
             whole = [[(prefix, 0, P)] + o for o in own]                  # ... and all of them: the prefix rows first
             if not stepping:
                 toks += [p + [f] for p, f in zip(prompts, first)] if max_new_tokens == 1 else prompts
             elif len(chunk) == 1 or not self._batch_decode_supported():
-                toks += [self._continue_single(prompts[j], first[j], whole[j], max_new_tokens, eos, req[j], lpr and lpr[j])
+                toks += [self._continue_single(prompts[j], first[j], whole[j], max_new_tokens, eos, req[j], lpr and lpr[j], rules)
                          for j in range(len(chunk))]
             else:
                 if decode == "shared":
@@ -2723,5 +2869,5 @@ class LeopardEngine:
                 for j in range(len(chunk)):
                     self._load_rows(own[j] if decode == "shared" else whole[j], st.k, st.v, j * st.capacity)
                 toks += self._greedy_loop_batch(st, prompts, first, [P + s for s in lens], max_new_tokens, eos, None if sampling is None else req,
-                                                own_lens=lens if decode == "shared" else None, lpr=lpr)
+                                                own_lens=lens if decode == "shared" else None, lpr=lpr, rules=rules)
         return self._outputs(toks, sfx, rows_all, [len(head) + int(t.numel()) for t in sfx])

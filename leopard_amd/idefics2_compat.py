@@ -160,7 +160,7 @@ class Idefics2ForConditionalGeneration:
         self.precision = "fast"
         self._engine: Optional[Idefics2Engine] = None
         self.device = torch.device("cpu")
-        self.generation_defaults: dict = {}              # do_sample / temperature / top_k / top_p of generation_config.json
+        self.generation_defaults: dict = {}              # do_sample / temperature / top_k / top_p / the logits rules of generation_config.json
         self.last_decoding = "greedy"
 
     @classmethod
@@ -268,14 +268,17 @@ class Idefics2ForConditionalGeneration:
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, pixel_values=None, pixel_attention_mask=None, max_new_tokens: int = 128,
                  eos_token_id=None, do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None,
-                 logprobs: Optional[int] = None, **unused):
+                 logprobs: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, **unused):
         """Greedy, or sampled with ``do_sample=True`` (HF semantics, generation_config.json defaults: leopard_amd.sampling).
+        ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens``: HF's logits processors inside the decode step (LeopardEngine's
+        LogitsRules; the ids seen are ``input_ids`` as passed, then the generated tokens); not together with ``logprobs``.
         ``logprobs`` = k in 0 .. 8: returns a ``sampling.GenerationLogprobs`` instead of the tensor (raw-logit log-softmax values: an id of
         ``suppress_tokens`` may appear among ``top_token_ids``, never as the generated token)."""
         k = self.engine._logprobs_arg("generate", logprobs)
         sampling.warn_unsupported("generate", unused)
         sp = sampling.resolve(self.generation_defaults, do_sample, temperature, top_k, top_p, seed)
-        self.last_decoding = sampling.describe(sp)
+        rules = sampling.resolve_rules(self.generation_defaults, repetition_penalty, no_repeat_ngram_size, min_new_tokens)
+        self.last_decoding = sampling.describe(sp, rules)
         if input_ids.shape[0] != 1:
             raise NotImplementedError("batch 1 per call, as in the reference script (IDEF:88-97)")
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
@@ -284,7 +287,7 @@ class Idefics2ForConditionalGeneration:
                                                                      self.config.vision_config.patch_size)
         eos = self.eos_token_id if eos_token_id is None else (tuple(eos_token_id) if isinstance(eos_token_id, (list, tuple)) else (int(eos_token_id),))
         out = self.engine.generate(input_ids.reshape(1, -1).to(self.device), images, max_new_tokens=max_new_tokens, eos_token_id=eos,
-                                   sampling=sp, logprobs=k)            # one cache + captured decode graph per engine (_generation_cache)
+                                   sampling=sp, logprobs=k, rules=rules)     # one cache + captured decode graph per engine (_generation_cache)
         if k is None:
             return out.to(input_ids.device)
         out.sequences = out.sequences.to(input_ids.device)

@@ -514,6 +514,28 @@ class Ops:
         self._check(self.lib.lmi_decode_logprobs(_ptr(logits), B, int(vocab), logits.stride(0), _ptr(tok), _ptr(hist_pos), ring, int(top_k),
                                                  _ptr(lp), _ptr(top_id), _ptr(top_lp), self._stream(logits)))
 
+    RULES_MAX_VOCAB = 262144           # LMI_RULES_MAX_VOCAB: lmi_decode_rules keeps one bit per id in 32 KB of LDS
+
+    def decode_rules(self, logits, vocab, seq, seq_len, penalty, ngram, min_left, tok=None, live=None, eos=None):
+        """lmi_decode_rules: before the choice kernel of a decode step, per row b of fp32 ``logits`` [B, ld], in place: append ``tok[b]`` to
+        ``seq[b]`` (``tok`` None: no append), repetition penalty ``penalty[b]`` over the ids seen, no-repeat n-gram ban of size ``ngram[b]``
+        (0 = off), eos banned while ``min_left[b]`` > 0 (then decremented); rows with ``live[b]`` == 0 are frozen.  seq int32 [B, seq_cap];
+        seq_len / ngram / min_left / live int32 [B]; penalty fp32 [B]; tok / eos int64."""
+        B = logits.shape[0]
+        if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+            raise TypeError(f"leopard_amd: decode_rules rewrites fp32 logits rows [B, ld], got {logits.dtype} {tuple(logits.shape)}")
+        if seq.dtype != torch.int32 or seq.dim() != 2 or seq.shape[0] < B or not seq.is_contiguous():
+            raise TypeError(f"leopard_amd: decode_rules seq must be a contiguous int32 [>= {B}, seq_cap], got {seq.dtype} {tuple(seq.shape)}")
+        for t, dt in ((seq_len, torch.int32), (penalty, torch.float32), (ngram, torch.int32), (min_left, torch.int32), (tok, torch.int64),
+                      (live, torch.int32)):
+            if t is not None and (t.dtype != dt or t.numel() < B):
+                raise TypeError(f"leopard_amd: decode_rules parameter must be {dt} with >= {B} entries, got {t.dtype} [{t.numel()}]")
+        if eos is not None and eos.dtype != torch.int64:
+            raise TypeError(f"leopard_amd: decode_rules eos must be int64, got {eos.dtype}")
+        self._check(self.lib.lmi_decode_rules(_ptr(logits), B, int(vocab), logits.stride(0), _ptr(tok), _ptr(live), _ptr(seq), _ptr(seq_len),
+                                              seq.shape[1], _ptr(penalty), _ptr(ngram), _ptr(min_left), _ptr(eos),
+                                              0 if eos is None else eos.numel(), self._stream(logits)))
+
     def gemm_ex(self, a, w, out, bias=None, epilogue=EPI_STORE, act=ACT_NONE, rowsq_in=None, norm_dim=0, norm_eps=0.0, norm_out=None,
                 norm_gamma=None, rowsq_out=None):
         """lmi_gemm with the RMSNorm folded in: consumer side (rowsq_in: [M, parts] fp32 partial sums of squares -> rows scaled

@@ -151,7 +151,7 @@ def _llava_class():
             finally:
                 cls._pending = None
             from .sampling import read_generation_config
-            m.generation_defaults = read_generation_config(path)      # HF: generate() takes do_sample / temperature / top_k / top_p from it
+            m.generation_defaults = read_generation_config(path)      # HF: generate() takes do_sample / temperature / top_k / top_p and the logits rules from it
             m._run_info = (path, torch_dtype, compute_dtype, recorded)
             return m
 
@@ -165,7 +165,8 @@ def _llava_class():
             return m
 
         def generate(self, *args, max_new_tokens=128, **kw):
-            # (``logprobs=k`` travels in kw: the return value is then the surface's GenerationLogprobs object)
+            # (``logprobs=k`` travels in kw: the return value is then the surface's GenerationLogprobs object; so do ``repetition_penalty``,
+            # ``no_repeat_ngram_size`` and ``min_new_tokens``, named parameters of the surface underneath)
             out = super().generate(*args, max_new_tokens=_cap_tokens(max_new_tokens), **kw)
             info = getattr(self, "_run_info", None)
             if info is not None and self.last_decoding != getattr(self, "_run_decoding", "greedy"):    # the side file says which rule RAN
@@ -197,7 +198,7 @@ def _idefics2_classes():
             return super().to(_device(device))
 
         def generate(self, *args, max_new_tokens=128, **kw):
-            # (``logprobs=k`` travels in kw, as above)
+            # (``logprobs=k`` and the three logits-rule arguments travel in kw, as above)
             out = super().generate(*args, max_new_tokens=_cap_tokens(max_new_tokens), **kw)
             info = getattr(self, "_run_info", None)
             if info is not None and self.last_decoding != getattr(self, "_run_decoding", "greedy"):    # the side file says which rule RAN

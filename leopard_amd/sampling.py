@@ -4,7 +4,8 @@ HF semantics: ``do_sample`` False or absent = greedy (bit-identical to the greed
 takes the checkpoint's generation_config.json value, else HF's default (temperature 1.0, top_k 50, top_p 1.0); ``temperature <= 0``
 with sampling raises ValueError.  The per-call seed comes from torch's default CPU generator (``torch.manual_seed(s)`` makes a run
 reproducible) unless ``seed=`` is passed.  Options this library does not implement (beam search, penalties, min-p, ...) produce one
-warning naming them instead of being ignored silently."""
+warning naming them instead of being ignored silently.  ``repetition_penalty``, ``no_repeat_ngram_size`` and ``min_new_tokens`` are
+implemented (LeopardEngine's LogitsRules): call arguments over generation_config.json over "off" (``resolve_rules``)."""
 from __future__ import annotations
 
 import json
@@ -15,11 +16,14 @@ from typing import List, Optional
 
 import torch
 
-from .engine import GenerateOutput, SamplingParams
+from .engine import GenerateOutput, LogitsRules, SamplingParams
 
 HF_DEFAULTS = {"temperature": 1.0, "top_k": 50, "top_p": 1.0}
 SAMPLING_KEYS = ("do_sample", "temperature", "top_k", "top_p")
-# generate() options that change the decoding rule and are not implemented, with the value that means "off"
+RULE_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens")       # LogitsRules: implemented (lmi_decode_rules)
+# generate() options that change the decoding rule and are not implemented, with the value that means "off".  The three RULE_KEYS are still
+# listed — warn_unsupported names whatever it is handed — but the generate() surfaces take them as named parameters (``resolve_rules``),
+# so they never reach it from there and no longer warn
 UNSUPPORTED = {"num_beams": 1, "num_beam_groups": 1, "penalty_alpha": None, "repetition_penalty": 1.0, "encoder_repetition_penalty": 1.0,
                "length_penalty": 1.0, "no_repeat_ngram_size": 0, "min_p": None, "typical_p": 1.0, "epsilon_cutoff": 0.0,
                "eta_cutoff": 0.0, "num_return_sequences": 1, "diversity_penalty": 0.0, "sequence_bias": None, "guidance_scale": None,
@@ -32,13 +36,13 @@ UNSUPPORTED = {"num_beams": 1, "num_beam_groups": 1, "penalty_alpha": None, "rep
 
 
 def read_generation_config(path: str) -> dict:
-    """The sampling keys of ``<path>/generation_config.json`` (empty when the file or the keys are absent)."""
+    """The sampling and logits-rule keys of ``<path>/generation_config.json`` (empty when the file or the keys are absent)."""
     gpath = os.path.join(str(path), "generation_config.json")
     if not os.path.exists(gpath):
         return {}
     with open(gpath) as f:
         g = json.load(f)
-    return {k: g[k] for k in SAMPLING_KEYS if g.get(k) is not None}
+    return {k: g[k] for k in SAMPLING_KEYS + RULE_KEYS if g.get(k) is not None}
 
 
 def warn_unsupported(where: str, kwargs: dict) -> None:
@@ -64,6 +68,16 @@ def resolve(defaults: Optional[dict] = None, do_sample=None, temperature=None, t
     return SamplingParams(float(t), int(k), float(p), int(seed))
 
 
+def resolve_rules(defaults: Optional[dict] = None, repetition_penalty=None, no_repeat_ngram_size=None,
+                  min_new_tokens=None) -> Optional[LogitsRules]:
+    """None = no rule; otherwise the LogitsRules of this call (call arguments over ``defaults`` — generation_config.json — over "off")."""
+    d = defaults or {}
+    pick = lambda v, key, off: v if v is not None else (d.get(key) if d.get(key) is not None else off)
+    rules = LogitsRules(float(pick(repetition_penalty, "repetition_penalty", 1.0)), int(pick(no_repeat_ngram_size, "no_repeat_ngram_size", 0)),
+                        int(pick(min_new_tokens, "min_new_tokens", 0)))
+    return rules if rules.active else None
+
+
 @dataclass
 class GenerationLogprobs:
     """What a generate() surface returns for one request with ``logprobs=k``: log-softmax values of the raw logits row each token was
@@ -86,5 +100,7 @@ def logprob_outputs(out: GenerateOutput) -> List[GenerationLogprobs]:
     return [GenerationLogprobs(s, lp, ti, tl) for s, lp, ti, tl in zip(seqs, out.token_logprobs, out.top_ids, out.top_logprobs)]
 
 
-def describe(params: Optional[SamplingParams]) -> str:
-    return "greedy" if params is None else params.describe()
+def describe(params: Optional[SamplingParams], rules: Optional[LogitsRules] = None) -> str:
+    """``greedy`` / ``sample(...)``, with the active rules appended (``greedy + repetition_penalty=1.2``)."""
+    base = "greedy" if params is None else params.describe()
+    return base if rules is None or not rules.active else base + " + " + rules.describe()

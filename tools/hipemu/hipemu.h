@@ -43,6 +43,7 @@ static inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) {
 void __syncthreads();
 // fibres switch only at rendezvous points, so a plain read-modify-write is atomic within the emulated workgroup
 template <typename T> static inline T atomicAdd(T* p, T v) { const T o = *p; *p = o + v; return o; }
+template <typename T> static inline T atomicOr(T* p, T v) { const T o = *p; *p = o | v; return o; }
 
 namespace hipemu {
 void launch(dim3 grid, dim3 block, size_t dyn_smem_bytes, const std::function<void()>& body);
