@@ -601,6 +601,44 @@ int lmi_decode_logprobs(const float* logits, int B, int vocab, int ld_logits, co
 int lmi_decode_rules(float* logits, int B, int vocab, int ld_logits, const int64_t* tok, const int* live, int* seq, int* seq_len, int seq_cap,
                      const float* penalty, const int* ngram, int* min_left, const int64_t* eos, int n_eos, void* stream);
 
+/* Beam search inside the decode step (generate_beams): the joint choice of num_beams beams over n_rows x vocab candidates — two launches
+ * behind this entry — for n_rows = num_beams live rows, or n_rows = 1 (the first token, from the prefill row: score[0] = 0, num_beams outputs).
+ *   row launch    one workgroup per row of RAW fp32 logits [n_rows, ld_logits] (columns [0, vocab)): row_lse[b] = the row's lse, the bits of
+ *                 lmi_token_logprobs; row_id / row_lp [b, j < num_beams] = the row's best entries that are neither an eos id nor on the
+ *                 suppress list, in the order value descending, id ascending (NaN never enters; -1 / -inf where there are fewer), and their
+ *                 logit - lse; row_eos_lp [b, j] = logit - lse of eos[j] (-inf when eos[j] is suppressed; NaN — never a candidate — for an
+ *                 entry < 0, outside the vocabulary or repeating an earlier one).  The logits are not modified.
+ *   select launch one wave over the n_rows x (num_beams + LMI_BEAM_MAX_EOS) candidates, total = score[b] + (logit - lse_b), one fp32 add, in
+ *                 the order total descending, beam ascending, id ascending (a NaN total never enters).  Candidate of rank r: a non-eos one
+ *                 becomes next beam j = 0 .. num_beams - 1 in that order — tok[j], parent[j], score[j] (the new accumulated log-probability)
+ *                 — and the walk ends with the one that fills beam num_beams - 1; every candidate up to there, eos ones included, is entry
+ *                 r of walk: walk[0] = the number of entries, then LMI_BEAM_WALK_ENTRY words each: rank, total (fp32 bits), parent, id,
+ *                 is_eos.  The host decides what an eos entry means (a finished hypothesis when r < num_beams).  Beams that the candidates
+ *                 cannot fill get tok 0, parent 0, score -inf.  pos[j] / k_len[j] (j < num_beams) and rows_held[0] += 1 (each nullable).
+ * eos int64 [LMI_BEAM_MAX_EOS] on the device, entries < 0 unused (another eos list never captures again); suppress int64 [n_suppress];
+ * score fp32 [max(n_rows, num_beams)] read then written; tok int64, parent int32 [num_beams]; walk int32 [LMI_BEAM_WALK_WORDS]; row_lse
+ * fp32 [n_rows]; row_id int32 / row_lp fp32 [n_rows, LMI_MAX_BEAMS]; row_eos_lp fp32 [n_rows, LMI_BEAM_MAX_EOS].  Exact with respect to a
+ * top-k over all n_rows x vocab candidates: a non-eos candidate outside its row's best num_beams is preceded by num_beams non-eos
+ * candidates of that row alone.  No atomics, no allocation, no host synchronisation: graph-capturable.  leopard_amd/csrc/beam.h. */
+#define LMI_MAX_BEAMS 8
+#define LMI_BEAM_MAX_EOS 4
+#define LMI_BEAM_WALK_ENTRY 5
+#define LMI_BEAM_WALK_WORDS (1 + (LMI_MAX_BEAMS + LMI_MAX_BEAMS * LMI_BEAM_MAX_EOS) * LMI_BEAM_WALK_ENTRY)
+int lmi_beam_step(const float* logits, int n_rows, int vocab, int ld_logits, const int64_t* suppress, int n_suppress, const int64_t* eos,
+                  int num_beams, float* score, int64_t* tok, int* parent, int* walk, float* row_lse, int* row_id, float* row_lp, float* row_eos_lp,
+                  int* pos, int* k_len, int* rows_held, void* stream);
+
+/* After lmi_beam_step: slot b of every K / V tensor continues from the rows of slot parent[b], in place and in ONE launch for all tensors.
+ * ptrs: device table of n_tensors base pointers (the K and V buffer of every layer); each holds num_beams slots of slot_rows rows of
+ * row_bytes bytes, rows contiguous.  Rows [row0[0], rows_held[0]) of every slot (device ints; clipped to slot_rows) are permuted:
+ * new slot b = old slot parent[b]; a thread owns one 16-byte chunk of one row index across the slots, loads all of them, then stores —
+ * no second buffer, no race.  Nothing outside that row range is read or written; an identity parent writes nothing.  max_rows (a
+ * multiple of 256) bounds rows_held[0] - row0[0] and sizes the grid: rows past row0[0] + max_rows are not permuted.  A parent entry outside
+ * [0, num_beams) keeps its slot.  LMI_EINVAL: null pointer, num_beams outside [1, LMI_MAX_BEAMS], row_bytes % 16 != 0, max_rows % 256 != 0.
+ * Graph-capturable.  leopard_amd/csrc/beam.h. */
+int lmi_beam_reorder(const void* ptrs, int n_tensors, const int* parent, int num_beams, const int* row0, const int* rows_held, int row_bytes,
+                     int slot_rows, int max_rows, void* stream);
+
 /* ---- multi-GPU: RCCL collectives over xGMI (SURVEY.md 8(b) "lmi_allgather / lmi_allreduce wrappers over RCCL communicators
  * ... created by lmi_comm_init(rank, nranks, unique_id) and freed by lmi_comm_destroy", 8(e)).  The reference's evaluation is one
  * process per GPU with no collective (run_eval_llava_siglip_multiimg.sh:9-11); its training side states the exchange pattern

@@ -69,6 +69,7 @@ class LeopardForConditionalGeneration:
         self.device = torch.device("cpu")
         self.generation_defaults: dict = {}              # do_sample / temperature / top_k / top_p / the logits rules of the checkpoint's generation_config.json
         self.last_decoding = "greedy"                    # the decoding rule of the last generate* call (leopard_amd.sampling.describe)
+        self.beam_defaults: dict = {}                    # num_beams / length_penalty / early_stopping of generation_config.json (generate_beams)
 
     # ---- loading ---------------------------------------------------------------------------------------------
     @classmethod
@@ -80,7 +81,7 @@ class LeopardForConditionalGeneration:
         cfg = load_config(path)
         m = cls(cfg, lambda dev, dt: CheckpointSource(path, dev, dt), compute_dtype, ops, torch_dtype=torch_dtype, precision=precision,
                 tp_rank=tp_rank, tp_size=tp_size)
-        m.generation_defaults = sampling.read_generation_config(path)
+        m.generation_defaults, m.beam_defaults = sampling.read_generation_defaults(path)
         return m
 
     def eval(self):
@@ -233,6 +234,22 @@ class LeopardForConditionalGeneration:
                                    logprobs=logprobs, rules=rules)
         return _with_logprobs(out, logprobs, one=True)
 
+    @torch.no_grad()
+    def generate_beams(self, input_ids, pixel_values=None, num_beams=None, max_new_tokens: int = 128, eos_token_id=None, length_penalty=None,
+                       early_stopping=None, num_return_sequences: int = 1, **unused):
+        """Beam search (HF's ``generate(num_beams=K, do_sample=False)``: LeopardEngine.generate_beams) with the prompt's K / V rows stored
+        once for all beams (``decode`` = "shared").  ``num_beams`` / ``length_penalty`` / ``early_stopping`` left unset take the
+        checkpoint's generation_config.json value, else HF's default (1, 1.0, False).  Returns the best sequence [1, n], or the list of
+        the ``num_return_sequences`` best, best first.  ``generate(num_beams=)`` itself still warns and decodes greedily."""
+        sampling.warn_unsupported("generate_beams", unused)
+        K, lp, es = sampling.resolve_beams(self.beam_defaults, num_beams, length_penalty, early_stopping)
+        if input_ids.shape[0] != 1:
+            raise NotImplementedError("batch 1 per call, as in the reference harness")
+        out = self.engine.generate_beams(input_ids.to(self.device), self._as_tiles(pixel_values), K, max_new_tokens=max_new_tokens,
+                                         eos_token_id=_eos_list(eos_token_id), length_penalty=lp, early_stopping=es,
+                                         num_return_sequences=num_return_sequences, decode="shared")
+        self.last_decoding = sampling.describe_beams(K, lp, es)
+        return sampling.beam_outputs(out, num_return_sequences, input_ids.device)
 
     @torch.no_grad()
     def generate_batch(self, requests: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], eos_token_id=None,

@@ -20,6 +20,7 @@
 #include "logprob.h"
 #include "decode_logprob.h"
 #include "decode_rules.h"
+#include "beam.h"
 
 using namespace lmi;
 
@@ -1862,6 +1863,50 @@ int lmi_decode_rules(float* logits, int B, int vocab, int ld_logits, const int64
     a.eos = eos; a.vocab = vocab; a.ld = ld_logits; a.seq_cap = seq_cap; a.n_eos = n_eos;
     LMI_LAUNCH(decode_rules_kernel, dim3(B), dim3(kRulesThreads), 0, stream, a);
     return check_launch("lmi_decode_rules");
+}
+
+int lmi_beam_step(const float* logits, int n_rows, int vocab, int ld_logits, const int64_t* suppress, int n_suppress, const int64_t* eos,
+                  int num_beams, float* score, int64_t* tok, int* parent, int* walk, float* row_lse, int* row_id, float* row_lp, float* row_eos_lp,
+                  int* pos, int* k_len, int* rows_held, void* stream) {
+    static_assert(kMaxBeams == LMI_MAX_BEAMS && kBeamMaxEos == LMI_BEAM_MAX_EOS && 1 + kBeamWalkMax * kBeamWalkWords == LMI_BEAM_WALK_WORDS,
+                  "the kernels' sizes are the header's constants");
+    if (!logits || !eos || !score || !tok || !parent || !walk || !row_lse || !row_id || !row_lp || !row_eos_lp)
+        return fail(LMI_EINVAL, "lmi_beam_step: null pointer");
+    if (num_beams < 1 || num_beams > LMI_MAX_BEAMS || (n_rows != 1 && n_rows != num_beams) || vocab <= 0 || ld_logits < vocab || (ld_logits & 3) ||
+        !aligned16(logits) || n_suppress < 0 || (n_suppress && !suppress))
+        return fail(LMI_EINVAL, "lmi_beam_step: bad argument (n_rows=%d num_beams=%d vocab=%d ld_logits=%d n_suppress=%d; num_beams in [1, %d], n_rows = 1 or "
+                    "num_beams, ld_logits >= vocab, ld_logits %% 4 == 0, 16-byte aligned logits)", n_rows, num_beams, vocab, ld_logits, n_suppress,
+                    LMI_MAX_BEAMS);
+    BeamRowsArgs r;
+    r.logits = logits; r.suppress = suppress; r.eos = eos; r.vocab = vocab; r.ld = ld_logits; r.n_suppress = n_suppress; r.K = num_beams;
+    r.row_lse = row_lse; r.row_id = row_id; r.row_lp = row_lp; r.row_eos_lp = row_eos_lp;
+    LMI_LAUNCH(beam_rows_kernel, dim3(n_rows), dim3(kLogprobThreads), 0, stream, r);
+    BeamSelectArgs s;
+    s.row_id = row_id; s.row_lp = row_lp; s.row_eos_lp = row_eos_lp; s.eos = eos; s.n_rows = n_rows; s.K = num_beams; s.score = score; s.tok = tok;
+    s.parent = parent; s.walk = walk; s.pos = pos; s.k_len = k_len; s.rows_held = rows_held;
+    LMI_LAUNCH(beam_select_kernel, dim3(1), dim3(64), 0, stream, s);
+    return check_launch("lmi_beam_step");
+}
+
+int lmi_beam_reorder(const void* ptrs, int n_tensors, const int* parent, int num_beams, const int* row0, const int* rows_held, int row_bytes,
+                     int slot_rows, int max_rows, void* stream) {
+    if (!ptrs || !parent || !row0 || !rows_held) return fail(LMI_EINVAL, "lmi_beam_reorder: null pointer");
+    if (n_tensors < 0 || n_tensors > 65535 || num_beams < 1 || num_beams > LMI_MAX_BEAMS || row_bytes <= 0 || (row_bytes & 15) || slot_rows < 0 ||
+        max_rows < 0 || (max_rows & 255) || (int64_t)max_rows * (row_bytes >> 4) / 256 > 0x7fffffffLL)
+        return fail(LMI_EINVAL, "lmi_beam_reorder: bad argument (n_tensors=%d num_beams=%d row_bytes=%d slot_rows=%d max_rows=%d; num_beams in [1, %d], "
+                    "row_bytes %% 16 == 0, max_rows %% 256 == 0)", n_tensors, num_beams, row_bytes, slot_rows, max_rows, LMI_MAX_BEAMS);
+    if (n_tensors == 0 || max_rows == 0 || slot_rows == 0 || num_beams == 1) return LMI_OK;
+    BeamReorderArgs a;
+    a.ptrs = (void* const*)ptrs; a.parent = parent; a.row0 = row0; a.rows_held = rows_held; a.K = num_beams; a.chunks_per_row = row_bytes >> 4;
+    a.slot_rows = slot_rows; a.slot_stride = (int64_t)slot_rows * (row_bytes >> 4);
+    const dim3 grid((unsigned)((int64_t)max_rows * a.chunks_per_row / 256), n_tensors);
+    switch (num_beams) {
+#define LMI_BEAM_REORDER(K_) case K_: LMI_LAUNCH(beam_reorder_kernel<K_>, grid, dim3(256), 0, stream, a); break
+        LMI_BEAM_REORDER(2); LMI_BEAM_REORDER(3); LMI_BEAM_REORDER(4); LMI_BEAM_REORDER(5); LMI_BEAM_REORDER(6); LMI_BEAM_REORDER(7);
+        LMI_BEAM_REORDER(8);
+#undef LMI_BEAM_REORDER
+    }
+    return check_launch("lmi_beam_reorder");
 }
 
 int lmi_gemv_rmsnorm(const void* W, const float* x, const float* norm_weight, float eps, void* out, int N, int K, int ldw,

@@ -126,6 +126,13 @@ class GenerateOutput:
                               [t for p in parts for t in p.top_logprobs])
 
 
+@dataclass
+class BeamOutput:
+    """What ``generate_beams`` returns: the ``num_return_sequences`` best finished hypotheses, best first."""
+    sequences: List[torch.Tensor]                # LongTensor [1, S_in + T_i] each, on the input's device
+    scores: List[float]                          # accumulated log-probability / T_i ** length_penalty (fp32 arithmetic, as transformers)
+
+
 class _LogprobRows:
     """Host side of one request's logprob rows: slices of the rings as they are drained, in token order."""
     def __init__(self, k: int):
@@ -282,6 +289,19 @@ class DecodeState:
     rule_ngram: Optional[torch.Tensor] = None    # int32 [B]
     rule_min_left: Optional[torch.Tensor] = None  # int32 [B]
     rule_eos: Optional[torch.Tensor] = None      # int64 [MAX_EOS], -1 = unused
+    # generate_beams: K = ``beams`` > 0 makes the step's tail lmi_beam_step + lmi_beam_reorder instead of the choice kernel.  All device
+    # memory, allocated by the first beam search on the state (_set_beams); the eos ids, the first row that can differ between slots and
+    # the rows held are device values, so another prompt or eos list never captures again
+    beams: int = 0
+    beam_score: Optional[torch.Tensor] = None    # fp32 [8]: the beams' accumulated log-probabilities
+    beam_parent: Optional[torch.Tensor] = None   # int32 [8]: the slot each new beam descends from
+    beam_walk: Optional[torch.Tensor] = None     # int32 [LMI_BEAM_WALK_WORDS]: the step's walk list, the ONE buffer the host reads per step
+    beam_rows: Optional[tuple] = None            # the row launch's outputs: (row_lse, row_id, row_lp, row_eos_lp)
+    beam_eos: Optional[torch.Tensor] = None      # int64 [4], -1 = unused
+    beam_row0: Optional[torch.Tensor] = None     # int32 [1]: 0 in a shared-prefix state, the prompt length in a copy state
+    beam_held: Optional[torch.Tensor] = None     # int32 [1]: the rows every slot holds
+    beam_ptrs: Optional[torch.Tensor] = None     # int64 [2 L]: the base pointers of st.k and st.v
+    beam_max_rows: int = 0                       # host bound on the divergent rows (a multiple of 256): the reorder launch's grid
     # the captured steps (LeopardEngine._run_step), keyed by (sampling, with logprobs): greedy / sampled, each without and with the logprobs
     # launch — the latter two with top_k = lp_k — and by (sampling, False, True) for the steps with the rules launch
     graphs: dict = field(default_factory=dict)
@@ -1781,6 +1801,12 @@ class LeopardEngine:
         """The tail of a decode step: lmi_decode_advance (greedy) or lmi_decode_sample (st.sampling) — the only difference between the two
         captured steps — after lmi_decode_rules when the call has rules (HF's order: processors, then suppress list, then warpers)."""
         V = self.cfg.text_config.vocab_size
+        if st.beams:                                                  # generate_beams: the beams choose jointly, then every slot's K / V rows follow
+            self.ops.beam_step(logits, V, st.beams, st.beam_eos, st.beam_score, st.tok, st.beam_parent, st.beam_walk, *st.beam_rows,
+                               suppress=self.suppress_tokens, pos=st.pos, k_len=kw.get("k_len"), rows_held=st.beam_held)
+            self.ops.beam_reorder(st.beam_ptrs, st.beam_parent, st.beams, st.beam_row0, st.beam_held, st.k[0].stride(0) * st.k[0].element_size(),
+                                  st.capacity, st.beam_max_rows)
+            return
         if st.rules:                                                  # generate(rules=...): one more launch, before the choice (it rewrites the rows)
             self.ops.decode_rules(logits, V, st.seq, st.seq_len, st.rule_pen, st.rule_ngram, st.rule_min_left, tok=st.tok, live=kw.get("live"),
                                   eos=st.rule_eos)
@@ -1964,10 +1990,13 @@ class LeopardEngine:
         if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs or not capturable:
             body()
             return
-        key = (st.sampling, st.logprobs is not None) + ((True,) if st.rules else ())
+        key = (st.sampling, st.logprobs is not None) + ((True,) if st.rules else ()) + ((("beams", st.beams, st.beam_max_rows),) if st.beams else ())
         if key not in st.graphs:
+            # (a beam step is first captured at the first step of a call, where no slot holds a row that can differ yet: the one row the
+            # warm-up run appends and permutes is written again by the replay)
             st.graphs[key], _ = self._capture_graph(body, restore + (() if st.logprobs is None else (st.lp_buf,)) +
-                                                    ((st.seq_len, st.rule_min_left) if st.rules else ()))
+                                                    ((st.seq_len, st.rule_min_left) if st.rules else ()) +
+                                                    ((st.beam_score, st.beam_parent, st.beam_walk, st.beam_held) if st.beams else ()))
         st.graphs[key].replay()
 
     def _decode_run(self, st, cache: KVCache):
@@ -2021,7 +2050,7 @@ class LeopardEngine:
     def decode_step(self, token_id: int, cache: KVCache) -> torch.Tensor:
         """Append one token: returns its logits [vocab] (fp32, a view of a static buffer) and advances the cache."""
         st = self._decode_state(cache)
-        st.sampling, st.logprobs, st.rules = False, None, False      # raw logits: never rules
+        st.sampling, st.logprobs, st.rules, st.beams = False, None, False, 0      # raw logits: never rules
         self._decode_seed(st, cache, token_id)
         self._decode_run(st, cache)
         cache.length += 1
@@ -2053,7 +2082,7 @@ class LeopardEngine:
         token's logprob row, read with one more small copy next to the token's."""
         out, nxt = list(prompt_ids), int(first)
         st = self._decode_state(cache)
-        st.sampling = sampling is not None
+        st.sampling, st.beams = sampling is not None, 0
         self._set_logprobs(st, None if lpr is None else lpr.k)
         self._set_rules(st, rules, eos)
         if rules is not None:
@@ -2317,7 +2346,7 @@ class LeopardEngine:
         st.pos.copy_(torch.tensor(seq_lens, dtype=torch.int32))
         st.k_len.copy_(torch.tensor([s + 1 for s in (own_lens or seq_lens)], dtype=torch.int32))
         st.live.fill_(1); st.budget.fill_(1 << 30); st.eos.fill_(-1); st.hist_pos.zero_()      # the host applies the stop rule here
-        st.sampling = sampling is not None
+        st.sampling, st.beams = sampling is not None, 0
         self._set_logprobs(st, None if lpr is None else lpr[0].k)
         self._set_rules(st, rules, eos)
         if rules is not None:
@@ -2394,7 +2423,7 @@ class LeopardEngine:
         if eos:
             st.eos[:len(eos)].copy_(torch.tensor(eos, dtype=torch.int64))
         st.live.zero_(); st.budget.zero_(); st.pos.zero_(); st.k_len.fill_(1); st.tok.zero_(); st.hist_pos.zero_()
-        st.sampling = sampling is not None
+        st.sampling, st.beams = sampling is not None, 0
         self._set_logprobs(st, k)
         self._set_rules(st, rules, eos)
         lpr = None if k is None else [None] * len(samples)          # a request's rows start with its first token's (admit)
@@ -2871,3 +2900,124 @@ class LeopardEngine:
                 toks += self._greedy_loop_batch(st, prompts, first, [P + s for s in lens], max_new_tokens, eos, None if sampling is None else req,
                                                 own_lens=lens if decode == "shared" else None, lpr=lpr, rules=rules)
         return self._outputs(toks, sfx, rows_all, [len(head) + int(t.numel()) for t in sfx])
+
+    # ------------------------------------------------------------------------------------------------
+    # Beam search: K hypotheses about one prompt are the K slots of a pooled decode state.  The step's tail chooses jointly over the K x V
+    # candidates (lmi_beam_step) and makes slot b continue from the K / V rows of the beam it descends from (lmi_beam_reorder: an in-place
+    # permutation of the rows that can differ); the host reads one small buffer per step — the walk list — and runs what transformers does
+    # after candidate selection (leopard_amd/beams.py).
+    # ------------------------------------------------------------------------------------------------
+    BEAMS_LO4 = "served"               # precision "lo4": the pair step serves B <= 8, and num_beams <= 8 always
+
+    def _set_beams(self, st, K: int, eos, row0: int, max_new_tokens: int) -> None:
+        """Make ``st`` the state of a beam search of K = st.B beams whose slots agree on rows [0, row0)."""
+        ops, dev = self.ops, self.device
+        if st.beam_walk is None:
+            st.beam_score = torch.zeros(ops.MAX_BEAMS, dtype=torch.float32, device=dev)
+            st.beam_parent = torch.zeros(ops.MAX_BEAMS, dtype=torch.int32, device=dev)
+            st.beam_walk = torch.zeros(ops.BEAM_WALK_WORDS, dtype=torch.int32, device=dev)
+            st.beam_rows = (torch.zeros(K, dtype=torch.float32, device=dev), torch.zeros(K, ops.MAX_BEAMS, dtype=torch.int32, device=dev),
+                            torch.zeros(K, ops.MAX_BEAMS, dtype=torch.float32, device=dev),
+                            torch.zeros(K, ops.BEAM_MAX_EOS, dtype=torch.float32, device=dev))
+            st.beam_eos = torch.full((ops.BEAM_MAX_EOS,), -1, dtype=torch.int64, device=dev)
+            st.beam_row0 = torch.zeros(1, dtype=torch.int32, device=dev)
+            st.beam_held = torch.zeros(1, dtype=torch.int32, device=dev)
+            st.beam_ptrs = torch.tensor([t.data_ptr() for t in st.k + st.v], dtype=torch.int64).to(dev)
+        st.beams, st.sampling = K, False
+        st.beam_max_rows = (max_new_tokens + 255) // 256 * 256
+        self._set_logprobs(st, None)
+        self._set_rules(st, None)
+        ids = sorted(eos)
+        st.beam_eos.copy_(torch.tensor(ids + [-1] * (ops.BEAM_MAX_EOS - len(ids)), dtype=torch.int64))
+        st.beam_score.zero_(); st.beam_parent.zero_()
+        st.beam_row0.fill_(row0); st.beam_held.fill_(row0)
+        st.live.fill_(1); st.budget.fill_(1 << 30); st.eos.fill_(-1); st.hist_pos.zero_()
+
+    @torch.no_grad()
+    def generate_beams(self, input_ids: torch.Tensor, tiles: Optional[torch.Tensor], num_beams: int, max_new_tokens: int = 128,
+                       eos_token_id: Sequence[int] = (128001, 128009), length_penalty: float = 1.0, early_stopping=False,
+                       num_return_sequences: int = 1, decode: str = "shared") -> BeamOutput:
+        """Beam search with ``num_beams`` = K beams (1 .. 8): transformers' ``generate(num_beams=K, do_sample=False)`` — its candidate
+        selection, its finished-hypothesis bookkeeping, ``length_penalty``, the three ``early_stopping`` values (False, True, "never") and
+        ``num_return_sequences`` <= K.  Among EXACT ties of the accumulated log-probability, which torch.topk leaves open, the order here
+        is beam ascending, then id ascending.  ``suppress_tokens`` applies as in HF's processors: the log-probabilities are those of the
+        raw row and a suppressed id is never a candidate.
+        One prefill of the prompt into a cache of P rows; the first K beams come from its last logits row; the steps run on a pooled decode
+        state of K slots, one captured step per token.  ``decode`` = "shared" (the default): the prompt's K / V rows are stored ONCE in the
+        state and read once per step for all beams (lmi_attn_decode_shared), the slots hold the generated rows only — needs what
+        ``generate_shared(decode="shared")`` needs (NotImplementedError otherwise; never a silent switch).  ``decode`` = "copy": every slot
+        holds the prompt rows too — K x (P + max_new_tokens) rows per layer — and the pooled attention runs, sliding window included.
+        Precision "lo4": served (the pair step, as for every batch of at most 8).  Refused before anything is launched: K outside 1 .. 8,
+        ``num_return_sequences`` > K, more than MAX_EOS eos ids, a vocabulary below (1 + n_eos) K, tensor-parallel, fp8 and "split" engines,
+        shapes without batched decode.  Returns a ``BeamOutput``."""
+        from .beams import BeamSearch, decode_walk
+        what, ops = "generate_beams", self.ops
+        if isinstance(num_beams, bool) or not isinstance(num_beams, (int, np.integer)) or not 1 <= int(num_beams) <= ops.MAX_BEAMS:
+            raise ValueError(f"{what}: num_beams must be an int in 1 .. {ops.MAX_BEAMS}, got {num_beams!r}")
+        K = int(num_beams)
+        if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, (int, np.integer)) or not 1 <= int(num_return_sequences) <= K:
+            raise ValueError(f"{what}: num_return_sequences must be in 1 .. num_beams = {K}, got {num_return_sequences!r}")
+        if decode not in ("copy", "shared"):
+            raise ValueError(f"{what}: decode must be 'copy' or 'shared', got {decode!r}")
+        if isinstance(max_new_tokens, bool) or int(max_new_tokens) < 1:
+            raise ValueError(f"{what}: max_new_tokens must be at least 1, got {max_new_tokens!r}")
+        if early_stopping not in (False, True, "never"):
+            raise ValueError(f"{what}: early_stopping must be False, True or 'never', got {early_stopping!r}")
+        V = self.cfg.text_config.vocab_size
+        eos = set(int(e) for e in eos_token_id if 0 <= int(e) < V)
+        if len(eos) > ops.BEAM_MAX_EOS or len(eos) > self.MAX_EOS:
+            raise ValueError(f"{what}: {len(eos)} eos ids (at most {min(ops.BEAM_MAX_EOS, self.MAX_EOS)} are held on the device)")
+        n_sup = 0 if self.suppress_tokens is None else int(self.suppress_tokens.numel())
+        if V - n_sup < (1 + len(eos)) * K:
+            raise ValueError(f"{what}: a vocabulary of {V} ids ({n_sup} suppressed) is below (1 + {len(eos)} eos ids) x {K} beams")
+        if self.tp_size > 1:
+            raise NotImplementedError(f"{what}: tensor-parallel engines are not supported (the beam launches and the pooled K / V slots belong to "
+                                      "the single-rank batched decode step)")
+        if self.fp8 is not None:
+            raise NotImplementedError(f"{what}: the fp8 schedule is not supported (the batched decode step has no fp8 form); use 'fast' or 'lo4'")
+        if self.split_operands:
+            raise NotImplementedError(f"{what}: precision 'split' is not supported (its attention hands over fp32 rows); use 'fast' or 'lo4'")
+        if decode == "shared":
+            self._continuation_guard(f"{what}(decode='shared')")
+            self._shared_decode_guard(K)
+        elif not self._batch_decode_supported():
+            raise NotImplementedError(f"{what}: this shape has no batched decode (lmi_gemm_skinny needs hidden and feed-forward widths that are "
+                                      "multiples of 128, the pooled decode attention head_dim 128)")
+        ids = input_ids.reshape(1, -1)
+        if ids.numel() == 0:
+            raise ValueError(f"{what}: the prompt is empty")
+        T = int(max_new_tokens)
+        P = self.merged_len(ids)
+        prefix = KVCache(self.cfg, P, self.dtype, self.device)
+        res = self.prefill(ids, tiles, cache=prefix)
+        if decode == "shared":
+            st = self._shared_state(K, T, P)
+            self._load_rows([(prefix, 0, P)], st.kp, st.vp, 0)        # the one prompt copy: the slots start with ZERO own rows
+            st.prefix_len.fill_(P)
+            row0 = 0
+        else:
+            st = self._batch_state(K, P + T)
+            for j in range(K):
+                self._load_rows([(prefix, 0, P)], st.k, st.v, j * st.capacity)
+            row0 = P
+        del prefix
+        self._set_beams(st, K, eos, row0, T)
+        st.pos.fill_(P); st.k_len.fill_(row0 + 1)
+        # the first token: the same entry, run eagerly on the ONE prefill row (score 0, K outputs) — HF's initial scores [0, -1e9, ..]
+        row = res.logits_last.reshape(1, -1).float()
+        if row.stride(1) != 1 or row.stride(0) % 4 or row.data_ptr() % 16:       # the kernel reads 16-byte aligned rows
+            pad = torch.zeros(1, (row.shape[1] + 3) // 4 * 4, dtype=torch.float32, device=row.device)
+            pad[:, :row.shape[1]] = row
+            row = pad
+        ops.beam_step(row, min(V, row.shape[1]), K, st.beam_eos, st.beam_score, st.tok, st.beam_parent, st.beam_walk,
+                      *(t[:1] for t in st.beam_rows), suppress=self.suppress_tokens)
+        search = BeamSearch(K, T, length_penalty, early_stopping, int(num_return_sequences))
+        try:
+            while search.step(decode_walk(st.beam_walk.cpu().numpy())):
+                self._batch_decode_run(st)
+        finally:
+            st.beams = 0                                              # the pooled state serves the other calls again, whatever happened
+        prompt = [int(t) for t in ids.reshape(-1).tolist()]
+        best = search.results()
+        return BeamOutput(sequences=[torch.tensor([prompt + seq], dtype=torch.int64, device=input_ids.device) for _, seq in best],
+                          scores=[float(sc) for sc, _ in best])

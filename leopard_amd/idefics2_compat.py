@@ -162,6 +162,7 @@ class Idefics2ForConditionalGeneration:
         self.device = torch.device("cpu")
         self.generation_defaults: dict = {}              # do_sample / temperature / top_k / top_p / the logits rules of generation_config.json
         self.last_decoding = "greedy"
+        self.beam_defaults: dict = {}                    # num_beams / length_penalty / early_stopping of generation_config.json (generate_beams)
 
     @classmethod
     def from_pretrained(cls, path: str, torch_dtype=torch.float16, ops: Optional[Ops] = None, patch_validity: str = "any",
@@ -181,7 +182,7 @@ class Idefics2ForConditionalGeneration:
         dtype = torch_dtype if torch_dtype in (torch.float16, torch.bfloat16) else torch.float16
         m = cls(cfg, lambda dev, dt: CheckpointSource(path, dev, dt), dtype, ops, eos, bad)
         m.patch_validity = patch_validity
-        m.generation_defaults = sampling.read_generation_config(path)
+        m.generation_defaults, m.beam_defaults = sampling.read_generation_defaults(path)
         from .compat import resolve_precision
         m.precision = resolve_precision(torch_dtype, dtype, precision)
         return m
@@ -292,3 +293,24 @@ class Idefics2ForConditionalGeneration:
             return out.to(input_ids.device)
         out.sequences = out.sequences.to(input_ids.device)
         return sampling.logprob_outputs(out)[0]
+
+    @torch.no_grad()
+    def generate_beams(self, input_ids, pixel_values=None, num_beams=None, max_new_tokens: int = 128, eos_token_id=None, length_penalty=None,
+                       early_stopping=None, num_return_sequences: int = 1, pixel_attention_mask=None, attention_mask=None, **unused):
+        """Beam search (HF's ``generate(num_beams=K, do_sample=False)``: LeopardEngine.generate_beams) with ``decode`` = "copy": every beam's
+        slot holds the prompt rows, which is what the sliding window of this model's decoder runs on.  ``num_beams`` / ``length_penalty``
+        / ``early_stopping`` left unset take generation_config.json's value, else HF's default (1, 1.0, False); ``bad_words_ids`` are never
+        candidates.  Returns the best sequence [1, n], or the list of the ``num_return_sequences`` best, best first."""
+        sampling.warn_unsupported("generate_beams", unused)
+        K, lp, es = sampling.resolve_beams(self.beam_defaults, num_beams, length_penalty, early_stopping)
+        if input_ids.shape[0] != 1:
+            raise NotImplementedError("batch 1 per call, as in the reference script (IDEF:88-97)")
+        if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
+            raise NotImplementedError("padded prompts are not produced by the reference script (batch 1)")
+        images = None if pixel_values is None else self.unpad_images(pixel_values, pixel_attention_mask, self.patch_validity,
+                                                                     self.config.vision_config.patch_size)
+        eos = self.eos_token_id if eos_token_id is None else (tuple(eos_token_id) if isinstance(eos_token_id, (list, tuple)) else (int(eos_token_id),))
+        out = self.engine.generate_beams(input_ids.reshape(1, -1).to(self.device), images, K, max_new_tokens=max_new_tokens, eos_token_id=eos,
+                                         length_penalty=lp, early_stopping=es, num_return_sequences=num_return_sequences, decode="copy")
+        self.last_decoding = sampling.describe_beams(K, lp, es)
+        return sampling.beam_outputs(out, num_return_sequences, input_ids.device)

@@ -536,6 +536,55 @@ class Ops:
                                               seq.shape[1], _ptr(penalty), _ptr(ngram), _ptr(min_left), _ptr(eos),
                                               0 if eos is None else eos.numel(), self._stream(logits)))
 
+    MAX_BEAMS = 8                      # LMI_MAX_BEAMS
+    BEAM_MAX_EOS = 4                   # LMI_BEAM_MAX_EOS: the device eos array of lmi_beam_step
+    BEAM_WALK_ENTRY = 5                # LMI_BEAM_WALK_ENTRY: rank, total (fp32 bits), parent, id, is_eos
+    BEAM_WALK_WORDS = 1 + (8 + 8 * 4) * 5   # LMI_BEAM_WALK_WORDS
+
+    def beam_step(self, logits, vocab, num_beams, eos, score, tok, parent, walk, row_lse, row_id, row_lp, row_eos_lp, suppress=None, pos=None,
+                  k_len=None, rows_held=None):
+        """lmi_beam_step: the joint choice of ``num_beams`` beams from fp32 ``logits`` [n_rows, ld] (n_rows = num_beams, or 1 for the first
+        token).  eos int64 [4] (-1 = unused); score fp32 [>= max(n_rows, num_beams)], read then written; tok int64 / parent int32
+        [>= num_beams]; walk int32 [BEAM_WALK_WORDS]; row_lse fp32 [n_rows]; row_id int32 / row_lp fp32 [n_rows, 8]; row_eos_lp fp32
+        [n_rows, 4]; pos / k_len int32 [>= num_beams] and rows_held int32 [1] are advanced by one."""
+        K = int(num_beams)
+        if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+            raise TypeError(f"leopard_amd: beam_step reads fp32 logits rows [n_rows, ld], got {logits.dtype} {tuple(logits.shape)}")
+        n = logits.shape[0]
+        if not 1 <= K <= self.MAX_BEAMS or n not in (1, K):
+            raise ValueError(f"leopard_amd: beam_step num_beams must be in [1, {self.MAX_BEAMS}] and n_rows 1 or num_beams, got {K} and {n} rows")
+        if eos.dtype != torch.int64 or eos.numel() != self.BEAM_MAX_EOS or not eos.is_contiguous():
+            raise TypeError(f"leopard_amd: beam_step eos must be a contiguous int64 [{self.BEAM_MAX_EOS}], got {eos.dtype} [{eos.numel()}]")
+        if suppress is not None and suppress.dtype != torch.int64:
+            raise TypeError(f"leopard_amd: beam_step suppress must be int64, got {suppress.dtype}")
+        for name, t, dt, need in (("score", score, torch.float32, max(n, K)), ("tok", tok, torch.int64, K), ("parent", parent, torch.int32, K),
+                                  ("walk", walk, torch.int32, self.BEAM_WALK_WORDS), ("row_lse", row_lse, torch.float32, n),
+                                  ("row_id", row_id, torch.int32, n * self.MAX_BEAMS), ("row_lp", row_lp, torch.float32, n * self.MAX_BEAMS),
+                                  ("row_eos_lp", row_eos_lp, torch.float32, n * self.BEAM_MAX_EOS), ("pos", pos, torch.int32, K),
+                                  ("k_len", k_len, torch.int32, K), ("rows_held", rows_held, torch.int32, 1)):
+            if t is not None and (t.dtype != dt or t.numel() < need or not t.is_contiguous()):
+                raise TypeError(f"leopard_amd: beam_step {name} must be a contiguous {dt} with >= {need} entries, got {t.dtype} [{t.numel()}]")
+        self._check(self.lib.lmi_beam_step(_ptr(logits), n, int(vocab), logits.stride(0), _ptr(suppress), 0 if suppress is None else suppress.numel(),
+                                           _ptr(eos), K, _ptr(score), _ptr(tok), _ptr(parent), _ptr(walk), _ptr(row_lse), _ptr(row_id), _ptr(row_lp),
+                                           _ptr(row_eos_lp), _ptr(pos), _ptr(k_len), _ptr(rows_held), self._stream(logits)))
+
+    def beam_reorder(self, ptrs, parent, num_beams, row0, rows_held, row_bytes, slot_rows, max_rows):
+        """lmi_beam_reorder: slot b of each of the tensors whose base pointers are in ``ptrs`` (int64 [n_tensors] on the device; num_beams
+        slots of ``slot_rows`` contiguous rows of ``row_bytes`` bytes each) takes rows [row0[0], rows_held[0]) of slot parent[b], in place.
+        parent int32 [>= num_beams]; row0 / rows_held int32 [1]; max_rows (a multiple of 256) bounds the rows permuted and sizes the grid."""
+        K = int(num_beams)
+        if not 1 <= K <= self.MAX_BEAMS:
+            raise ValueError(f"leopard_amd: beam_reorder num_beams must be in [1, {self.MAX_BEAMS}], got {K}")
+        if ptrs.dtype != torch.int64 or ptrs.dim() != 1 or not ptrs.is_contiguous():
+            raise TypeError(f"leopard_amd: beam_reorder ptrs must be a contiguous int64 [n_tensors], got {ptrs.dtype} {tuple(ptrs.shape)}")
+        for name, t, need in (("parent", parent, K), ("row0", row0, 1), ("rows_held", rows_held, 1)):
+            if t.dtype != torch.int32 or t.numel() < need or not t.is_contiguous():
+                raise TypeError(f"leopard_amd: beam_reorder {name} must be a contiguous int32 with >= {need} entries, got {t.dtype} [{t.numel()}]")
+        if int(row_bytes) <= 0 or int(row_bytes) % 16 or int(max_rows) < 0 or int(max_rows) % 256 or int(slot_rows) < 0:
+            raise ValueError(f"leopard_amd: beam_reorder needs row_bytes % 16 == 0 and max_rows % 256 == 0, got {row_bytes} and {max_rows}")
+        self._check(self.lib.lmi_beam_reorder(_ptr(ptrs), ptrs.numel(), _ptr(parent), K, _ptr(row0), _ptr(rows_held), int(row_bytes), int(slot_rows),
+                                              int(max_rows), self._stream(ptrs)))
+
     def gemm_ex(self, a, w, out, bias=None, epilogue=EPI_STORE, act=ACT_NONE, rowsq_in=None, norm_dim=0, norm_eps=0.0, norm_out=None,
                 norm_gamma=None, rowsq_out=None):
         """lmi_gemm with the RMSNorm folded in: consumer side (rowsq_in: [M, parts] fp32 partial sums of squares -> rows scaled

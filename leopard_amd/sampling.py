@@ -21,6 +21,8 @@ from .engine import GenerateOutput, LogitsRules, SamplingParams
 HF_DEFAULTS = {"temperature": 1.0, "top_k": 50, "top_p": 1.0}
 SAMPLING_KEYS = ("do_sample", "temperature", "top_k", "top_p")
 RULE_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens")       # LogitsRules: implemented (lmi_decode_rules)
+BEAM_KEYS = ("num_beams", "length_penalty", "early_stopping")                     # generate_beams: implemented (lmi_beam_step)
+BEAM_DEFAULTS = {"num_beams": 1, "length_penalty": 1.0, "early_stopping": False}  # HF's
 # generate() options that change the decoding rule and are not implemented, with the value that means "off".  The three RULE_KEYS are still
 # listed — warn_unsupported names whatever it is handed — but the generate() surfaces take them as named parameters (``resolve_rules``),
 # so they never reach it from there and no longer warn
@@ -35,21 +37,29 @@ UNSUPPORTED = {"num_beams": 1, "num_beam_groups": 1, "penalty_alpha": None, "rep
                "output_scores": False, "output_logits": False, "output_attentions": False}
 
 
-def read_generation_config(path: str) -> dict:
-    """The sampling and logits-rule keys of ``<path>/generation_config.json`` (empty when the file or the keys are absent)."""
+def read_generation_defaults(path: str):
+    """(sampling and logits-rule keys, beam-search keys) of ``<path>/generation_config.json``, read once: what ``generate*`` and
+    ``generate_beams`` take when a call leaves them unset (both empty when the file is absent)."""
     gpath = os.path.join(str(path), "generation_config.json")
     if not os.path.exists(gpath):
-        return {}
+        return {}, {}
     with open(gpath) as f:
         g = json.load(f)
-    return {k: g[k] for k in SAMPLING_KEYS + RULE_KEYS if g.get(k) is not None}
+    return tuple({k: g[k] for k in keys if g.get(k) is not None} for keys in (SAMPLING_KEYS + RULE_KEYS, BEAM_KEYS))
+
+
+def read_generation_config(path: str, beams: bool = False) -> dict:
+    """The sampling and logits-rule keys of ``<path>/generation_config.json`` (empty when the file or the keys are absent); with ``beams``
+    the beam-search keys instead (BEAM_KEYS)."""
+    return read_generation_defaults(path)[1 if beams else 0]
 
 
 def warn_unsupported(where: str, kwargs: dict) -> None:
     bad = sorted(k for k, off in UNSUPPORTED.items() if k in kwargs and kwargs[k] is not None and kwargs[k] != off)
     if bad:
+        hint = "; for beam search use generate_beams()" if "num_beams" in bad and where != "generate_beams" else ""
         warnings.warn(f"{where}: {', '.join(bad)} {'is' if len(bad) == 1 else 'are'} not supported by leopard_amd and ignored "
-                      "(decoding is greedy or temperature / top-k / top-p sampling)", UserWarning, stacklevel=3)
+                      f"(decoding is greedy or temperature / top-k / top-p sampling{hint})", UserWarning, stacklevel=3)
 
 
 def resolve(defaults: Optional[dict] = None, do_sample=None, temperature=None, top_k=None, top_p=None,
@@ -76,6 +86,25 @@ def resolve_rules(defaults: Optional[dict] = None, repetition_penalty=None, no_r
     rules = LogitsRules(float(pick(repetition_penalty, "repetition_penalty", 1.0)), int(pick(no_repeat_ngram_size, "no_repeat_ngram_size", 0)),
                         int(pick(min_new_tokens, "min_new_tokens", 0)))
     return rules if rules.active else None
+
+
+def resolve_beams(defaults: Optional[dict] = None, num_beams=None, length_penalty=None, early_stopping=None):
+    """(num_beams, length_penalty, early_stopping) of a ``generate_beams`` call: call arguments over ``defaults`` (generation_config.json)
+    over HF's defaults (1, 1.0, False)."""
+    d = defaults or {}
+    pick = lambda v, key: v if v is not None else (d[key] if d.get(key) is not None else BEAM_DEFAULTS[key])
+    return int(pick(num_beams, "num_beams")), float(pick(length_penalty, "length_penalty")), pick(early_stopping, "early_stopping")
+
+
+def describe_beams(num_beams: int, length_penalty: float, early_stopping=False) -> str:
+    """``beam(4, length_penalty=1.0)``, with ``early_stopping`` appended when it is not HF's default."""
+    return f"beam({num_beams}, length_penalty={length_penalty}" + ("" if early_stopping is False else f", early_stopping={early_stopping!r}") + ")"
+
+
+def beam_outputs(out, num_return_sequences: int, device):
+    """An engine ``BeamOutput`` as the surfaces return it: the best sequence [1, n], or the list when ``num_return_sequences`` > 1."""
+    seqs = [s.to(device) for s in out.sequences]
+    return seqs[0] if int(num_return_sequences) == 1 else seqs
 
 
 @dataclass
