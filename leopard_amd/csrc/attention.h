@@ -699,7 +699,10 @@ __global__ void __launch_bounds__(ATT_THREADS, 2) attn_fwd_dma_kernel(AttnArgs p
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int d = db * 32 + 8 * (r >> 2) + 4 * fh + (r & 3);
-                const float y = o_acc[db][r] * inv;
+                // sep_rn: the residual is taken against the 16-bit value the rows below store — the conversion of the ROUNDED fp32 product.
+                // Fused with the multiply (one rounding) the conversion picks the other neighbour where the product rounds onto a 16-bit
+                // midpoint, and the image then corrects that element by a whole 16-bit step the wrong way.
+                const float y = sep_rn(o_acc[db][r] * inv);
                 lo[r] = d < D ? y - (float)(T)y : 0.f;
                 amax = fmaxf(amax, __builtin_fabsf(lo[r]));
             }

@@ -80,11 +80,13 @@ __global__ void __launch_bounds__(Attn64Geom<NBLK>::NT, 3 - NBLK) attn_fwd_r64_k
     typedef typename vec_of<T>::x8 T8;
     constexpr int NKS = G::NKS, NDB = G::NDB, NW = G::NW, PPW = G::PPW, ROWB = G::ROWB;
     constexpr bool ASM_QK = (NBLK == 2);                           // scores through the inline-asm MFMA (see mfma32_sv); O and Q pinned in AGPRs
-    // where the diagonal / tail masks go.  NBLK == 1: after the region that produced the scores, followed by the masked maxima (exact: a
-    // row's reference never exceeds its visible maximum).  NBLK == 2: before the region that exponentiates them, the in-region maxima being
-    // taken over unmasked scores (a reference somewhat above the visible maximum is valid, only less tight): with 250 live registers any
-    // extra code between the asm MFMAs and the next region makes hipcc spill scores right behind an MFMA it does not know to be one.
-    constexpr bool MASK_AFTER = (NBLK == 1);
+    // where the diagonal / tail masks go: after the region that produced the scores, followed by the masked maxima (exact: a row's
+    // reference never exceeds its visible maximum).  NBLK == 2 used to mask before the region that exponentiates the scores and kept the
+    // in-region maxima of the UNMASKED scores as the reference; that is only valid while no hidden key outscores the visible ones by much:
+    // a hidden key ~11 above every visible one put the reference so high that the visible keys' P underflowed in f16 on their way into the
+    // P.V MFMA (tests/attn_entries_ref.py: the x4 values and the key-after / key-before probes).  The masked steps are the few on the
+    // diagonal, the tail and the window edge; the scores they read were finished by the PV half of the region (or by mfma_result_nops).
+    constexpr bool MASK_AFTER = true;
     LMI_DYN_SMEM(smem);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();

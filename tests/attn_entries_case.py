@@ -1,6 +1,10 @@
 """Test helper: the fixed calls behind tests/golden/attn_entries_emu_bits.json — every attention entry of the library through ``Ops`` at the smallest
 shapes at which a host decision flips (split geometry, GQA packing, own-pass instantiation, kernel choice, output kind), in f16 and bf16.  Inputs are made
-by integer arithmetic only, so every machine builds the same bits; ``run_all`` returns a SHA-256 per output tensor."""
+by integer arithmetic only, so every machine builds the same bits; ``run_all`` returns a SHA-256 per output tensor.
+
+Every case function takes its input tensors (``inp``, default: the ``*_inputs`` function of the same name) and its allocation (``mem``: ``Plain``,
+the digest path, or ``Guarded``) from the caller; ``launch`` returns the inputs together with the outputs.  tests/attn_entries_ref.py builds the
+value tests on that, over CASES and the value-only EXTRA cases."""
 import contextlib
 import hashlib
 
@@ -41,88 +45,151 @@ def _option(ops, key, value):
         ops.set_option(key, old)
 
 
-def decode(ops, dt, dev, q_lens, k_lens, H=4, KV=1, window=0, pooled=False, hl=False, D=128):
+GUARD = 7.0
+
+
+class Plain:
+    """Allocation of the digest path: zeroed outputs and workspaces of exactly the launch's size."""
+
+    def __init__(self, dev):
+        self.dev = dev
+
+    def out(self, rows, cols, dtype=torch.float32):
+        return torch.zeros(rows, cols, dtype=dtype, device=self.dev)
+
+    def ws(self, n):
+        return torch.zeros(n, device=self.dev)
+
+
+class Guarded(Plain):
+    """Allocation of the value-test path: a guard row behind every output tensor (the rows themselves start out zero, as Plain's do: a
+    row-selected image keeps its initial bytes) and workspaces filled with NaN."""
+
+    def __init__(self, dev):
+        super().__init__(dev)
+        self.full = []
+
+    def out(self, rows, cols, dtype=torch.float32):
+        t = torch.zeros(rows + 1, cols, dtype=dtype)
+        t[rows:] = GUARD
+        self.full.append(t.to(self.dev))
+        return self.full[-1][:rows]
+
+    def ws(self, n):
+        return torch.full((n,), float("nan"), device=self.dev)
+
+    def intact(self):
+        return all(bool((t[-1] == GUARD).all()) for t in self.full)
+
+
+def decode_inputs(dt, dev, q_lens, k_lens, H=4, KV=1, pooled=False, D=128, **_):
+    """q rows packed; k / v packed (cu_k) or, pooled, slot s owning rows [s * stride, s * stride + k_len[s]) with stride = max_k + 3."""
+    rows = len(q_lens) * (max(k_lens) + 3) if pooled else sum(k_lens)
+    return {"q": _rows(sum(q_lens), H * D, dt, dev, 1), "k": _rows(rows, KV * D, dt, dev, 2), "v": _rows(rows, KV * D, dt, dev, 3)}
+
+
+def decode(ops, dt, dev, q_lens, k_lens, H=4, KV=1, window=0, pooled=False, hl=False, D=128, inp=None, mem=None):
     """attention_decode (packed sequences) or attention_decode_pool (slots of one pooled cache, one query row each)."""
+    inp, mem = inp or decode_inputs(dt, dev, q_lens, k_lens, H, KV, pooled, D), mem or Plain(dev)
     n, tq, max_k = len(q_lens), sum(q_lens), max(k_lens)
-    q = _rows(tq, H * D, dt, dev, 1)
-    out = torch.zeros(2 * tq if hl else tq, H * D, dtype=dt, device=dev)
+    q, k, v = inp["q"], inp["k"], inp["v"]
+    out = mem.out(2 * tq if hl else tq, H * D, dt)
+    ws = mem.ws(ops.decode_workspace_elems(tq, H, D, max_k))
     if pooled:
         stride = max_k + 3                                           # slot s owns rows [s * stride, s * stride + k_len[s])
-        k, v = _rows(n * stride, KV * D, dt, dev, 2), _rows(n * stride, KV * D, dt, dev, 3)
-        ws = torch.zeros(ops.decode_workspace_elems(tq, H, D, max_k), device=dev)
         ops.attention_decode_pool(q, k, v, out, _cu(q_lens, dev), _i32([s * stride for s in range(n)], dev), _i32(k_lens, dev), max_k, H, KV, D,
                                   D ** -0.5, ws, window=window, hl=hl)
     else:
-        k, v = _rows(sum(k_lens), KV * D, dt, dev, 2), _rows(sum(k_lens), KV * D, dt, dev, 3)
-        ws = torch.zeros(ops.decode_workspace_elems(tq, H, D, max_k), device=dev)
         ops.attention_decode(q, k, v, out, _cu(q_lens, dev), _cu(k_lens, dev), max(q_lens), max_k, H, KV, D, D ** -0.5, ws, window=window, hl=hl)
     return {"out": out}
 
 
-def shared(ops, dt, dev, k_lens, max_prefix, prefix=None, max_k=None, H=4, KV=1, hl=False, D=128):
+def shared_inputs(dt, dev, k_lens, max_prefix, max_k=None, H=4, KV=1, D=128, **_):
+    n, max_k = len(k_lens), max(k_lens) if max_k is None else max_k
+    return {"q": _rows(n, H * D, dt, dev, 1), "kp": _rows(max_prefix, KV * D, dt, dev, 4), "vp": _rows(max_prefix, KV * D, dt, dev, 5),
+            "k": _rows(n * (max_k + 3), KV * D, dt, dev, 2), "v": _rows(n * (max_k + 3), KV * D, dt, dev, 3)}
+
+
+def shared(ops, dt, dev, k_lens, max_prefix, prefix=None, max_k=None, H=4, KV=1, hl=False, D=128, inp=None, mem=None):
     """attention_decode_shared: sequence s = row s of q, behind ``prefix`` (device) <= max_prefix shared rows."""
+    inp, mem = inp or shared_inputs(dt, dev, k_lens, max_prefix, max_k, H, KV, D), mem or Plain(dev)
     n, max_k = len(k_lens), max(k_lens) if max_k is None else max_k
     stride = max_k + 3
-    q = _rows(n, H * D, dt, dev, 1)
-    kp, vp = _rows(max_prefix, KV * D, dt, dev, 4), _rows(max_prefix, KV * D, dt, dev, 5)
-    k, v = _rows(n * stride, KV * D, dt, dev, 2), _rows(n * stride, KV * D, dt, dev, 3)
-    out = torch.zeros(2 * n if hl else n, H * D, dtype=dt, device=dev)
-    ws = torch.zeros(ops.decode_shared_workspace_elems(n, H, D, max_prefix, max_k), device=dev)
-    ops.attention_decode_shared(q, kp, vp, _i32([max_prefix if prefix is None else prefix], dev), max_prefix, k, v, out,
-                                _i32([s * stride for s in range(n)], dev), _i32(k_lens, dev), max_k, H, KV, D, D ** -0.5, ws, hl=hl)
+    out = mem.out(2 * n if hl else n, H * D, dt)
+    ws = mem.ws(ops.decode_shared_workspace_elems(n, H, D, max_prefix, max_k))
+    ops.attention_decode_shared(inp["q"], inp["kp"], inp["vp"], _i32([max_prefix if prefix is None else prefix], dev), max_prefix, inp["k"], inp["v"],
+                                out, _i32([s * stride for s in range(n)], dev), _i32(k_lens, dev), max_k, H, KV, D, D ** -0.5, ws, hl=hl)
     return {"out": out}
 
 
-def prefix_rows(ops, dt, dev, k_lens, prefix, f32=False, H=4, KV=1, D=128):
-    """attention_prefix_rows: row r sees the prefix and k_len[r] pooled rows from k_begin[r] (overlapping ranges, as a continuation's rows have)."""
+def prefix_rows_inputs(dt, dev, k_lens, prefix, H=4, KV=1, D=128, **_):
     n, max_k = len(k_lens), max(max(k_lens), 1)
-    q = _rows(n, H * D, dt, dev, 1)
-    kp, vp = _rows(prefix, KV * D, dt, dev, 4), _rows(prefix, KV * D, dt, dev, 5)
-    k, v = _rows(2 * n + max_k, KV * D, dt, dev, 2), _rows(2 * n + max_k, KV * D, dt, dev, 3)
-    out = torch.zeros(n, H * D, dtype=dt, device=dev)
-    out32 = torch.zeros(n, H * D, device=dev) if f32 else None
-    ws = torch.zeros(ops.prefix_rows_workspace_elems(n, H, D, prefix, max_k), device=dev)
-    ops.attention_prefix_rows(q, kp, vp, prefix, k, v, out, _i32([2 * r for r in range(n)], dev), _i32(k_lens, dev), max_k, H, KV, D, D ** -0.5, ws,
-                              out_f32=out32)
+    return {"q": _rows(n, H * D, dt, dev, 1), "kp": _rows(prefix, KV * D, dt, dev, 4), "vp": _rows(prefix, KV * D, dt, dev, 5),
+            "k": _rows(2 * n + max_k, KV * D, dt, dev, 2), "v": _rows(2 * n + max_k, KV * D, dt, dev, 3)}
+
+
+def prefix_rows(ops, dt, dev, k_lens, prefix, f32=False, H=4, KV=1, D=128, inp=None, mem=None):
+    """attention_prefix_rows: row r sees the prefix and k_len[r] pooled rows from k_begin[r] = 2 r (overlapping ranges, as a continuation's rows have)."""
+    inp, mem = inp or prefix_rows_inputs(dt, dev, k_lens, prefix, H, KV, D), mem or Plain(dev)
+    n, max_k = len(k_lens), max(max(k_lens), 1)
+    out = mem.out(n, H * D, dt)
+    out32 = mem.out(n, H * D) if f32 else None
+    ws = mem.ws(ops.prefix_rows_workspace_elems(n, H, D, prefix, max_k))
+    ops.attention_prefix_rows(inp["q"], inp["kp"], inp["vp"], prefix, inp["k"], inp["v"], out, _i32([2 * r for r in range(n)], dev), _i32(k_lens, dev),
+                              max_k, H, KV, D, D ** -0.5, ws, out_f32=out32)
     return {"out": out, "out_f32": out32} if f32 else {"out": out}
 
 
-def _lo4_act(rows, H, D, dt, dev, sel):
+def _lo4_act(rows, H, D, dt, dev, sel, mem):
+    k4 = lo4_head_k4(H, D)
+    act = Lo4Act(mem.out(rows, H * D, dt), mem.out(rows, k4 // 2, torch.uint8), mem.out(rows, k4 // 32, torch.uint8))
     if sel is not None:
         row_sel = torch.tensor([1 if sel(r) else 0 for r in range(rows)], dtype=torch.uint8)
         unit_sel = torch.tensor([int(row_sel[u * 64:(u + 1) * 64].any()) for u in range((rows + 63) // 64)], dtype=torch.uint8)
-        sel = (row_sel.to(dev), unit_sel.to(dev))
-    act = Lo4Act.empty(rows, H * D, dt, dev, k4=lo4_head_k4(H, D), sel=sel)
-    act.hi.zero_(), act.img.zero_(), act.sc.zero_()
+        act.row_sel, act.unit_sel = row_sel.to(dev), unit_sel.to(dev)
     return act
 
 
-def varlen(ops, dt, dev, q_lens, k_lens=None, D=128, H=4, KV=1, causal=True, window=0, kind="out", sel=None):
-    """The varlen forward: self-attention (cu_k is cu_q) or, with k_lens, keys of their own; kind = out | f32 | fp8 | lo4."""
+def varlen_inputs(dt, dev, q_lens, k_lens=None, D=128, H=4, KV=1, **_):
     tq, tk = sum(q_lens), sum(q_lens if k_lens is None else k_lens)
-    q, k, v = _rows(tq, H * D, dt, dev, 1), _rows(tk, KV * D, dt, dev, 2), _rows(tk, KV * D, dt, dev, 3)
+    return {"q": _rows(tq, H * D, dt, dev, 1), "k": _rows(tk, KV * D, dt, dev, 2), "v": _rows(tk, KV * D, dt, dev, 3)}
+
+
+def varlen(ops, dt, dev, q_lens, k_lens=None, D=128, H=4, KV=1, causal=True, window=0, kind="out", sel=None, inp=None, mem=None):
+    """The varlen forward: self-attention (cu_k is cu_q) or, with k_lens, keys of their own; kind = out | f32 | fp8 | lo4."""
+    inp, mem = inp or varlen_inputs(dt, dev, q_lens, k_lens, D, H, KV), mem or Plain(dev)
+    tq = sum(q_lens)
+    q, k, v = inp["q"], inp["k"], inp["v"]
     cu_q = _cu(q_lens, dev)
     cu_k = cu_q if k_lens is None else _cu(k_lens, dev)
     args = (cu_q, cu_k, max(q_lens), H, KV, D, D ** -0.5, causal)
     if kind == "f32":
-        return {"out_f32": ops.attention_f32out(q, k, v, torch.zeros(tq, H * D, device=dev), *args, window=window)}
+        return {"out_f32": ops.attention_f32out(q, k, v, mem.out(tq, H * D), *args, window=window)}
     if kind == "fp8":
-        return {"out_fp8": ops.attention_fp8out(q, k, v, torch.zeros(tq, H * D, dtype=torch.uint8, device=dev), 16.0, *args, window=window)}
+        return {"out_fp8": ops.attention_fp8out(q, k, v, mem.out(tq, H * D, torch.uint8), 16.0, *args, window=window)}
     if kind == "lo4":
-        act = ops.attention_lo4(q, k, v, _lo4_act(tq, H, D, dt, dev, sel), *args, window=window)
+        act = ops.attention_lo4(q, k, v, _lo4_act(tq, H, D, dt, dev, sel, mem), *args, window=window)
         return {"out": act.hi, "img": act.img, "scales": act.sc}
-    return {"out": ops.attention(q, k, v, torch.zeros(tq, H * D, dtype=dt, device=dev), *args, window=window)}
+    return {"out": ops.attention(q, k, v, mem.out(tq, H * D, dt), *args, window=window)}
 
 
-def prefix_fwd(ops, dt, dev, q_lens, prefix, sel=None, lo4=False, H=4, KV=1, D=128):
+def prefix_fwd_inputs(dt, dev, q_lens, prefix, H=4, KV=1, D=128, **_):
     tq = sum(q_lens)
-    q, k, v = _rows(tq, H * D, dt, dev, 1), _rows(tq, KV * D, dt, dev, 2), _rows(tq, KV * D, dt, dev, 3)
-    kp, vp = _rows(prefix, KV * D, dt, dev, 4), _rows(prefix, KV * D, dt, dev, 5)
+    return {"q": _rows(tq, H * D, dt, dev, 1), "k": _rows(tq, KV * D, dt, dev, 2), "v": _rows(tq, KV * D, dt, dev, 3),
+            "kp": _rows(prefix, KV * D, dt, dev, 4), "vp": _rows(prefix, KV * D, dt, dev, 5)}
+
+
+def prefix_fwd(ops, dt, dev, q_lens, prefix, sel=None, lo4=False, H=4, KV=1, D=128, inp=None, mem=None):
+    inp, mem = inp or prefix_fwd_inputs(dt, dev, q_lens, prefix, H, KV, D), mem or Plain(dev)
+    tq = sum(q_lens)
+    q, k, v, kp, vp = inp["q"], inp["k"], inp["v"], inp["kp"], inp["vp"]
     if lo4:
-        act = ops.attention_prefix_lo4(q, k, v, kp, vp, prefix, _lo4_act(tq, H, D, dt, dev, sel), _cu(q_lens, dev), max(q_lens), H, KV, D, D ** -0.5)
+        act = ops.attention_prefix_lo4(q, k, v, kp, vp, prefix, _lo4_act(tq, H, D, dt, dev, sel, mem), _cu(q_lens, dev), max(q_lens), H, KV, D, D ** -0.5)
         return {"out": act.hi, "img": act.img, "scales": act.sc}
-    return {"out": ops.attention_prefix(q, k, v, kp, vp, prefix, torch.zeros(tq, H * D, dtype=dt, device=dev), _cu(q_lens, dev), max(q_lens), H, KV, D,
-                                        D ** -0.5)}
+    return {"out": ops.attention_prefix(q, k, v, kp, vp, prefix, mem.out(tq, H * D, dt), _cu(q_lens, dev), max(q_lens), H, KV, D, D ** -0.5)}
+
+
+INPUTS = {decode: decode_inputs, shared: shared_inputs, prefix_rows: prefix_rows_inputs, varlen: varlen_inputs, prefix_fwd: prefix_fwd_inputs}
 
 
 LONG_PREFIX = 57 * 64 - 20          # 57 tiles: more than the 56 splits the prefix pass may take with one kv head, so pre_tiles becomes 2
@@ -187,15 +254,48 @@ CASES = {
 }
 
 
-def run_case(ops, name, dtype, device="cpu"):
-    """{output name: sha256 hex of the tensor's bytes} of one case in one dtype."""
-    fn, kw, options = CASES[name]
+_R64 = {"attn.rows64_min": 0}
+EDGE_LENS = [63, 64, 65, 127, 128, 129, 1]          # one below, at and one above the 64-key tile and the 128-row query block
+# Value-only cases (tests/attn_entries_ref.py): never digested, so the golden fixture keeps listing exactly CASES.
+EXTRA = {
+    "x_varlen_edges_h4_kv1": (varlen, dict(q_lens=EDGE_LENS), {}),
+    "x_varlen_edges_h8_kv2": (varlen, dict(q_lens=EDGE_LENS, H=8, KV=2), {}),
+    "x_varlen_window1": (varlen, dict(q_lens=[20, 130], window=1), {}),
+    "x_varlen_window64": (varlen, dict(q_lens=[20, 130], window=64), {}),
+    "x_varlen_window65": (varlen, dict(q_lens=[20, 130], window=65), {}),
+    "x_varlen_window_above_all": (varlen, dict(q_lens=[20, 130], window=131), {}),
+    "x_varlen_cross_causal_plus1": (varlen, dict(q_lens=[5, 0, 40], k_lens=[6, 0, 41]), {}),
+    "x_varlen_cross_causal_plus64": (varlen, dict(q_lens=[5, 0, 40], k_lens=[69, 0, 104]), {}),
+    **{f"x_decode_window{w}": (decode, dict(q_lens=[1, 2], k_lens=[200, 90], window=w), {}) for w in (1, 90, 91, 200, 201)},
+    **{f"x_pool_window{w}": (decode, dict(q_lens=[1, 1], k_lens=[200, 90], pooled=True, window=w), {}) for w in (1, 90, 91, 200, 201)},
+    # the software-pipelined kernels (256-row blocks): one block and a part, a sequence below one block, with and without a window
+    **{f"x_rows64_{r}_window{w}": (varlen, dict(q_lens=[300, 40, 70], window=w), dict(_R64, **{"attn.rows64": r})) for r in (1, 2) for w in (0, 33)},
+    **{f"x_prefix_fwd_p{p}": (prefix_fwd, dict(q_lens=[1, 128, 129], prefix=p), {}) for p in (63, 64, 65)},
+}
+
+
+def make_inputs(fn, kw, dtype, device="cpu"):
+    """The case's own (integer-hash) input tensors: {"q", "k", "v"[, "kp", "vp"]}."""
+    return INPUTS[fn](DTYPES[dtype], device, **kw)
+
+
+def launch(ops, fn, kw, options, dtype, device="cpu", inp=None, mem=None, **more):
+    """One launch of a case (``more``: keyword arguments that replace the case's) on the caller's inputs (default: the case's own) with the
+    caller's allocation (default: Plain).  Returns (inputs, outputs), the device synchronised."""
+    kw = dict(kw, **more)
+    inp = make_inputs(fn, kw, dtype, device) if inp is None else inp
     with contextlib.ExitStack() as stack:
         for key, value in options.items():
             stack.enter_context(_option(ops, key, value))
-        outs = fn(ops, DTYPES[dtype], device, **kw)
+        outs = fn(ops, DTYPES[dtype], device, inp=inp, mem=mem, **kw)
         if device != "cpu":
             torch.cuda.synchronize()
+    return inp, outs
+
+
+def run_case(ops, name, dtype, device="cpu"):
+    """{output name: sha256 hex of the tensor's bytes} of one case in one dtype."""
+    outs = launch(ops, *CASES[name], dtype, device)[1]
     return {key: hashlib.sha256(t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest() for key, t in outs.items()}
 
 
