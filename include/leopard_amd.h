@@ -628,6 +628,29 @@ int lmi_beam_step(const float* logits, int n_rows, int vocab, int ld_logits, con
                   int num_beams, float* score, int64_t* tok, int* parent, int* walk, float* row_lse, int* row_id, float* row_lp, float* row_eos_lp,
                   int* pos, int* k_len, int* rows_held, void* stream);
 
+/* lmi_beam_step with the logits processors of lmi_decode_rules (generate_beams(rules=...)).  In beam search transformers applies the
+ * processors to the log-softmax scores, not to the logits: log_softmax -> processors -> + beam score.  Row b, with raw logits x:
+ *   append    append_tok non-null and seq_len[b] < seq_cap: seq[b][seq_len[b]] = append_tok[b], seq_len[b] += 1 (read before the select launch
+ *             writes tok: append_tok may be tok).  L = seq_len[b].
+ *   lse       row_lse[b]: the bits of lmi_token_logprobs / lmi_beam_step for the raw row.  s[i] = x[i] - lse, one fp32 subtract.
+ *   penalty   penalty[b] != 1: every id of seq[b][0 .. L) in [0, vocab), once however often it occurs: s < 0 ? s * p : s / p (one fp32
+ *             multiply or IEEE divide).
+ *   n-gram    ngram[b] = n > 0, L + 1 >= n: -inf on every id that completes a seen n-gram (lmi_decode_rules' rule; ids outside [0, vocab)
+ *             are compared and never written).
+ *   minimum   min_left[b] > 0: -inf on every used eos id, then min_left[b] -= 1.
+ *   row_id / row_lp [b, j < num_beams] = the best entries of the processed row s' that are neither eos nor suppressed, s' descending, id
+ *   ascending (among ids no rule touches the order is taken on the raw logits); a -inf entry is an ordinary candidate that comes last, NaN
+ *   never enters, -1 / -inf where there are fewer.  row_eos_lp [b, j] = s'[eos[j]] (-inf when suppressed, NaN for an unused slot).
+ * The select launch and every other argument are lmi_beam_step's.  The logits are not modified; ONE pass over each row.  seq int32
+ * [n_rows, seq_cap]; seq_len / ngram / min_left int32 [n_rows]; penalty fp32 [n_rows] (> 0): all device values.  The id lists follow the
+ * beams by one lmi_beam_reorder launch over seq (16-byte rows of four ids).  LMI_EINVAL: lmi_beam_step's, a null rule pointer (append_tok
+ * excepted), seq_cap < 1, vocab > LMI_RULES_MAX_VOCAB (two bitmaps of one bit per id in 64 KB of LDS).  Graph-capturable.
+ * leopard_amd/csrc/beam.h. */
+int lmi_beam_step_rules(const float* logits, int n_rows, int vocab, int ld_logits, const int64_t* suppress, int n_suppress, const int64_t* eos,
+                        int num_beams, float* score, int64_t* tok, int* parent, int* walk, float* row_lse, int* row_id, float* row_lp,
+                        float* row_eos_lp, int* pos, int* k_len, int* rows_held, const int64_t* append_tok, int* seq, int* seq_len, int seq_cap,
+                        const float* penalty, const int* ngram, int* min_left, void* stream);
+
 /* After lmi_beam_step: slot b of every K / V tensor continues from the rows of slot parent[b], in place and in ONE launch for all tensors.
  * ptrs: device table of n_tensors base pointers (the K and V buffer of every layer); each holds num_beams slots of slot_rows rows of
  * row_bytes bytes, rows contiguous.  Rows [row0[0], rows_held[0]) of every slot (device ints; clipped to slot_rows) are permuted:

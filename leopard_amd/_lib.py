@@ -101,6 +101,7 @@ SIGNATURES = {
     "lmi_decode_logprobs": [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P],
     "lmi_decode_rules": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P],
     "lmi_beam_step": [_P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "lmi_beam_step_rules": [_P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "lmi_beam_reorder": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _P],
     "lmi_comm_unique_id": [_P],
     "lmi_comm_init": [_I, _I, _P, C.POINTER(C.c_void_p)],

@@ -236,19 +236,22 @@ class LeopardForConditionalGeneration:
 
     @torch.no_grad()
     def generate_beams(self, input_ids, pixel_values=None, num_beams=None, max_new_tokens: int = 128, eos_token_id=None, length_penalty=None,
-                       early_stopping=None, num_return_sequences: int = 1, **unused):
+                       early_stopping=None, num_return_sequences: int = 1, repetition_penalty=None, no_repeat_ngram_size=None,
+                       min_new_tokens=None, **unused):
         """Beam search (HF's ``generate(num_beams=K, do_sample=False)``: LeopardEngine.generate_beams) with the prompt's K / V rows stored
-        once for all beams (``decode`` = "shared").  ``num_beams`` / ``length_penalty`` / ``early_stopping`` left unset take the
+        once for all beams (``decode`` = "shared").  ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens``: HF's logits
+        processors on every beam's log-softmax scores (call arguments over generation_config.json over "off").  ``num_beams`` / ``length_penalty`` / ``early_stopping`` left unset take the
         checkpoint's generation_config.json value, else HF's default (1, 1.0, False).  Returns the best sequence [1, n], or the list of
         the ``num_return_sequences`` best, best first.  ``generate(num_beams=)`` itself still warns and decodes greedily."""
         sampling.warn_unsupported("generate_beams", unused)
         K, lp, es = sampling.resolve_beams(self.beam_defaults, num_beams, length_penalty, early_stopping)
+        rules = sampling.resolve_rules(self.generation_defaults, repetition_penalty, no_repeat_ngram_size, min_new_tokens)
         if input_ids.shape[0] != 1:
             raise NotImplementedError("batch 1 per call, as in the reference harness")
         out = self.engine.generate_beams(input_ids.to(self.device), self._as_tiles(pixel_values), K, max_new_tokens=max_new_tokens,
                                          eos_token_id=_eos_list(eos_token_id), length_penalty=lp, early_stopping=es,
-                                         num_return_sequences=num_return_sequences, decode="shared")
-        self.last_decoding = sampling.describe_beams(K, lp, es)
+                                         num_return_sequences=num_return_sequences, decode="shared", rules=rules)
+        self.last_decoding = sampling.describe_beams(K, lp, es) + ("" if rules is None else " + " + rules.describe())
         return sampling.beam_outputs(out, num_return_sequences, input_ids.device)
 
     @torch.no_grad()

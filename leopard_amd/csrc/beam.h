@@ -21,8 +21,12 @@
 // index of one K or V tensor ACROSS the K slots: it loads the K values into registers, then stores val[parent[b]] into every slot b
 // with parent[b] != b — the permutation is in place and free of races by construction (nobody else touches these K chunks).  Rows
 // outside [*row0, *rows_held) are never read or written; an identity parent returns after reading it.
+//
+// lmi_beam_step_rules is lmi_beam_step with HF's logits processors between the log-softmax and the beam scores: its row launch is
+// beam_rows_rules_kernel (below, after beam_rows_kernel), its select launch is beam_select_kernel unchanged.
 #pragma once
 #include "decode_logprob.h"
+#include "decode_rules.h"
 
 namespace lmi {
 
@@ -108,6 +112,184 @@ __global__ void __launch_bounds__(kLogprobThreads) beam_rows_kernel(BeamRowsArgs
             }
             a.row_eos_lp[b * kBeamMaxEos + j] = lp;
         }
+    }
+}
+
+// Row launch with the logits processors (beam_rows_rules_kernel, lmi_beam_step_rules).  In beam search transformers applies the processors
+// to log_softmax(row), not to the row: s = logit - lse, then the penalty on s, the n-gram ban, the eos ban — so the penalty needs the lse
+// FIRST, and the lse is that of the raw row.  Still one pass over the row:
+//   1. append   tok[b] joins seq[b] (decode_rules_kernel's rule: the token this step consumes).
+//   2. touched  two vocab-bit bitmaps in LDS, built from the ids alone: ``seen`` (ids of the sequence inside [0, vocab); only with a penalty)
+//               and ``ban`` (ids that complete a seen n-gram).  No logit is read.
+//   3. scan     beam_rows_kernel's pass over the RAW row — the lse has its bits — whose top list also skips the touched ids: among ids no
+//               rule touches, s = logit - lse is monotone in the logit, so their best K are found before the lse exists.
+//   4. touched  with the lse known, the bitmap words (vocab / 32 of them, not the row) are walked: a touched id that is neither eos nor
+//               suppressed offers s' = -inf (banned) or the penalised s (seen) to a second list.
+//   5. merge    thread 0: the untouched list as logit - lse and the touched lists through one TopList — (s' descending, id ascending) is a
+//               strict total order, so the result is one set whatever the merge order.  The eos values are s' of each eos id: penalised
+//               when seen, -inf when banned by an n-gram, suppressed or while min_left[b] > 0; then min_left[b] -= 1.
+// A -inf entry is an ordinary candidate that comes last; a row whose lse is NaN or -inf offers nothing (every s is NaN).
+struct BeamRulesArgs {
+    const int64_t* tok;           // [n_rows] nullable: the token this step consumes
+    int* seq;                     // [n_rows, seq_cap]
+    int* seq_len;                 // [n_rows]
+    const float* penalty;         // [n_rows]
+    const int* ngram;             // [n_rows]
+    int* min_left;                // [n_rows]
+    int seq_cap;
+};
+
+__global__ void __launch_bounds__(kLogprobThreads) beam_rows_rules_kernel(BeamRowsArgs a, BeamRulesArgs u) {
+    constexpr int NW = kLogprobThreads / 64, K = kMaxTopLogprobs;
+    __shared__ uint32_t seen[kRulesMaxVocab / 32], ban[kRulesMaxVocab / 32];
+    __shared__ float red_m[NW], red_s[NW], red_v[NW * K];
+    __shared__ int red_i[NW * K];
+    __shared__ int len_s;
+    __shared__ float lse_s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (int)(blockDim.x >> 6), nt = (int)blockDim.x;
+    const float* row = a.logits + (int64_t)b * (int64_t)a.ld;
+    int* seq = u.seq + (int64_t)b * (int64_t)u.seq_cap;
+    const int V = a.vocab, words = (V + 31) / 32;
+    const float p = u.penalty[b];
+    const int n = u.ngram[b];
+    const int min_left = u.min_left[b];           // read by every thread before the first barrier; written after the last one
+    const bool use_p = p != 1.f;
+    int64_t eos[kBeamMaxEos];
+#pragma unroll
+    for (int j = 0; j < kBeamMaxEos; ++j) eos[j] = a.eos[j];
+    auto barred = [&](int i) {
+        bool hit = false;
+#pragma unroll
+        for (int j = 0; j < kBeamMaxEos; ++j) hit = hit || eos[j] == (int64_t)i;
+        for (int j = 0; j < a.n_suppress; ++j) hit = hit || a.suppress[j] == (int64_t)i;
+        return hit;
+    };
+
+    // 1. append
+    if (tid == 0) {
+        int L = u.seq_len[b];
+        L = L < 0 ? 0 : (L > u.seq_cap ? u.seq_cap : L);
+        if (u.tok && L < u.seq_cap) {
+            seq[L] = (int)u.tok[b];
+            u.seq_len[b] = ++L;
+        }
+        len_s = L;
+    }
+    for (int w = tid; w < words; w += nt) { seen[w] = 0u; ban[w] = 0u; }
+    __syncthreads();
+    const int L = len_s;
+
+    // 2. the touched ids
+    if (use_p) {
+        for (int i = tid; i < L; i += nt) {
+            const int id = seq[i];
+            if (id >= 0 && id < V) atomicOr(&seen[id >> 5], 1u << (id & 31));
+        }
+    }
+    if (n > 0 && L + 1 >= n) {
+        const int m = n - 1;                      // the ids to match: seq[L - m .. L)
+        const int* tail = seq + (L - m);
+        for (int i = tid; i < L - m; i += nt) {
+            int k = 0;
+            while (k < m && seq[i + k] == tail[k]) ++k;
+            if (k < m) continue;
+            const int id = seq[i + m];
+            if (id >= 0 && id < V) atomicOr(&ban[id >> 5], 1u << (id & 31));
+        }
+    }
+    __syncthreads();
+
+    // 3. the one pass over the raw row
+    float m = -INFINITY, s = 0.f;
+    TopList top;
+    top.clear();
+    lse_scan_lane(row, V, m, s, [&](float x, int i) {
+        if (top_before(x, i, top.v[K - 1], top.i[K - 1]) && !(((seen[i >> 5] | ban[i >> 5]) >> (i & 31)) & 1u) && !barred(i)) top.insert(x, i);
+    });
+    lse_wave_merge(m, s);
+    auto wave_top_merge = [&](TopList& t) {
+#pragma unroll
+        for (int k = 32; k >= 1; k >>= 1) {
+            float ov[K];
+            int oi[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) { ov[j] = shfl_xor(t.v[j], k); oi[j] = shfl_xor(t.i[j], k); }
+#pragma unroll
+            for (int j = 0; j < K; ++j) t.offer(ov[j], oi[j]);
+        }
+    };
+    wave_top_merge(top);
+    if (lane == 0) {
+        red_m[wave] = m; red_s[wave] = s;
+#pragma unroll
+        for (int j = 0; j < K; ++j) { red_v[wave * K + j] = top.v[j]; red_i[wave * K + j] = top.i[j]; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < nw; ++w)
+            for (int j = 0; j < K; ++j) top.offer(red_v[w * K + j], red_i[w * K + j]);
+        lse_s = lse_block_finish(m, s, red_m, red_s, nw);
+    }
+    __syncthreads();                              // the lse is known; red_v / red_i have been read
+    const float l = lse_s;
+
+    // 4. the touched ids, from the bitmaps
+    auto ruled = [&](int id) {                    // s' of a touched id
+        const uint32_t bit = 1u << (id & 31);
+        float v = row[id] - l;
+        if (seen[id >> 5] & bit) v = v < 0.f ? v * p : v / p;
+        if (ban[id >> 5] & bit) v = -INFINITY;
+        return v;
+    };
+    TopList hit;
+    hit.clear();
+    for (int w = tid; w < words; w += nt) {
+        uint32_t bits = seen[w] | ban[w];
+        while (bits) {
+            const int id = w * 32 + __builtin_ctz(bits);
+            bits &= bits - 1;
+            if (!barred(id)) hit.offer(ruled(id), id);
+        }
+    }
+    wave_top_merge(hit);
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) { red_v[wave * K + j] = hit.v[j]; red_i[wave * K + j] = hit.i[j]; }
+    }
+    __syncthreads();
+
+    // 5. merge and write
+    if (tid == 0) {
+        TopList fin;
+        fin.clear();
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (top.i[j] != 0x7fffffff) fin.offer(top.v[j] - l, top.i[j]);
+        for (int w = 0; w < nw; ++w)
+            for (int j = 0; j < K; ++j) fin.offer(red_v[w * K + j], red_i[w * K + j]);
+        a.row_lse[b] = l;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (j < a.K) {
+                const bool empty = fin.i[j] == 0x7fffffff;
+                a.row_id[b * K + j] = empty ? -1 : fin.i[j];
+                a.row_lp[b * K + j] = empty ? -INFINITY : fin.v[j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kBeamMaxEos; ++j) {
+            const int64_t e = eos[j];
+            float lp = NAN;                                          // unused slot / id outside the vocabulary / a repeat of an earlier slot
+            bool use = e >= 0 && e < (int64_t)V;
+            for (int q = 0; q < j; ++q) use = use && eos[q] != e;
+            if (use) {
+                bool sup = min_left > 0;
+                for (int q = 0; q < a.n_suppress; ++q) sup = sup || a.suppress[q] == e;
+                lp = sup ? -INFINITY : ruled((int)e);
+            }
+            a.row_eos_lp[b * kBeamMaxEos + j] = lp;
+        }
+        if (min_left > 0) u.min_left[b] = min_left - 1;
     }
 }
 

@@ -1888,6 +1888,33 @@ int lmi_beam_step(const float* logits, int n_rows, int vocab, int ld_logits, con
     return check_launch("lmi_beam_step");
 }
 
+int lmi_beam_step_rules(const float* logits, int n_rows, int vocab, int ld_logits, const int64_t* suppress, int n_suppress, const int64_t* eos,
+                        int num_beams, float* score, int64_t* tok, int* parent, int* walk, float* row_lse, int* row_id, float* row_lp,
+                        float* row_eos_lp, int* pos, int* k_len, int* rows_held, const int64_t* append_tok, int* seq, int* seq_len, int seq_cap,
+                        const float* penalty, const int* ngram, int* min_left, void* stream) {
+    if (!logits || !eos || !score || !tok || !parent || !walk || !row_lse || !row_id || !row_lp || !row_eos_lp || !seq || !seq_len || !penalty ||
+        !ngram || !min_left)
+        return fail(LMI_EINVAL, "lmi_beam_step_rules: null pointer");
+    if (num_beams < 1 || num_beams > LMI_MAX_BEAMS || (n_rows != 1 && n_rows != num_beams) || vocab <= 0 || ld_logits < vocab || (ld_logits & 3) ||
+        !aligned16(logits) || n_suppress < 0 || (n_suppress && !suppress) || seq_cap < 1)
+        return fail(LMI_EINVAL, "lmi_beam_step_rules: bad argument (n_rows=%d num_beams=%d vocab=%d ld_logits=%d n_suppress=%d seq_cap=%d; num_beams in "
+                    "[1, %d], n_rows = 1 or num_beams, ld_logits >= vocab, ld_logits %% 4 == 0, 16-byte aligned logits, seq_cap >= 1)", n_rows,
+                    num_beams, vocab, ld_logits, n_suppress, seq_cap, LMI_MAX_BEAMS);
+    if (vocab > LMI_RULES_MAX_VOCAB)
+        return fail(LMI_EINVAL, "lmi_beam_step_rules: vocab %d exceeds %d (two bits per id in 64 KB of LDS)", vocab, LMI_RULES_MAX_VOCAB);
+    BeamRowsArgs r;
+    r.logits = logits; r.suppress = suppress; r.eos = eos; r.vocab = vocab; r.ld = ld_logits; r.n_suppress = n_suppress; r.K = num_beams;
+    r.row_lse = row_lse; r.row_id = row_id; r.row_lp = row_lp; r.row_eos_lp = row_eos_lp;
+    BeamRulesArgs u;
+    u.tok = append_tok; u.seq = seq; u.seq_len = seq_len; u.penalty = penalty; u.ngram = ngram; u.min_left = min_left; u.seq_cap = seq_cap;
+    LMI_LAUNCH(beam_rows_rules_kernel, dim3(n_rows), dim3(kLogprobThreads), 0, stream, r, u);
+    BeamSelectArgs s;
+    s.row_id = row_id; s.row_lp = row_lp; s.row_eos_lp = row_eos_lp; s.eos = eos; s.n_rows = n_rows; s.K = num_beams; s.score = score; s.tok = tok;
+    s.parent = parent; s.walk = walk; s.pos = pos; s.k_len = k_len; s.rows_held = rows_held;
+    LMI_LAUNCH(beam_select_kernel, dim3(1), dim3(64), 0, stream, s);
+    return check_launch("lmi_beam_step_rules");
+}
+
 int lmi_beam_reorder(const void* ptrs, int n_tensors, const int* parent, int num_beams, const int* row0, const int* rows_held, int row_bytes,
                      int slot_rows, int max_rows, void* stream) {
     if (!ptrs || !parent || !row0 || !rows_held) return fail(LMI_EINVAL, "lmi_beam_reorder: null pointer");

@@ -302,8 +302,13 @@ class DecodeState:
     beam_held: Optional[torch.Tensor] = None     # int32 [1]: the rows every slot holds
     beam_ptrs: Optional[torch.Tensor] = None     # int64 [2 L]: the base pointers of st.k and st.v
     beam_max_rows: int = 0                       # host bound on the divergent rows (a multiple of 256): the reorder launch's grid
+    # generate_beams(rules=...): the step's tail is lmi_beam_step_rules over ``seq`` and the rule parameters above (every slot starts with
+    # the prompt's ids), then one more lmi_beam_reorder over ``seq`` in 16-byte chunks of four ids — 4 bytes x the slot's id capacity x K
+    beam_id_ptr: Optional[torch.Tensor] = None   # int64 [1]: the base pointer of ``seq``
+    beam_id_chunks: Optional[torch.Tensor] = None  # int32 [2]: the chunk that holds the first generated id, the chunks a finished call holds
     # the captured steps (LeopardEngine._run_step), keyed by (sampling, with logprobs): greedy / sampled, each without and with the logprobs
-    # launch — the latter two with top_k = lp_k — and by (sampling, False, True) for the steps with the rules launch
+    # launch — the latter two with top_k = lp_k — and by (sampling, False, True) for the steps with the rules launch; a beam step adds
+    # ("beams", K, reorder bound) to its key, without and with rules
     graphs: dict = field(default_factory=dict)
     lp_k: Optional[int] = None                   # the top_k the two logprobs graphs were captured with (another k captures them again)
     graph_failed: bool = False                   # tensor parallel: the capture failed once, the step runs eagerly (_decode_run)
@@ -1802,10 +1807,18 @@ class LeopardEngine:
         captured steps — after lmi_decode_rules when the call has rules (HF's order: processors, then suppress list, then warpers)."""
         V = self.cfg.text_config.vocab_size
         if st.beams:                                                  # generate_beams: the beams choose jointly, then every slot's K / V rows follow
-            self.ops.beam_step(logits, V, st.beams, st.beam_eos, st.beam_score, st.tok, st.beam_parent, st.beam_walk, *st.beam_rows,
-                               suppress=self.suppress_tokens, pos=st.pos, k_len=kw.get("k_len"), rows_held=st.beam_held)
+            if st.rules:                                              # ... from the processed rows, and every slot's id list follows too
+                self.ops.beam_step_rules(logits, V, st.beams, st.beam_eos, st.beam_score, st.tok, st.beam_parent, st.beam_walk, *st.beam_rows,
+                                         st.seq, st.seq_len, st.rule_pen, st.rule_ngram, st.rule_min_left, append=st.tok,
+                                         suppress=self.suppress_tokens, pos=st.pos, k_len=kw.get("k_len"), rows_held=st.beam_held)
+            else:
+                self.ops.beam_step(logits, V, st.beams, st.beam_eos, st.beam_score, st.tok, st.beam_parent, st.beam_walk, *st.beam_rows,
+                                   suppress=self.suppress_tokens, pos=st.pos, k_len=kw.get("k_len"), rows_held=st.beam_held)
             self.ops.beam_reorder(st.beam_ptrs, st.beam_parent, st.beams, st.beam_row0, st.beam_held, st.k[0].stride(0) * st.k[0].element_size(),
                                   st.capacity, st.beam_max_rows)
+            if st.rules:                                              # the id lists: 16-byte "rows" of four ids, from the prompt's last chunk on
+                self.ops.beam_reorder(st.beam_id_ptr, st.beam_parent, st.beams, st.beam_id_chunks[:1], st.beam_id_chunks[1:], 16,
+                                      st.seq.shape[1] // 4, st.beam_max_rows)
             return
         if st.rules:                                                  # generate(rules=...): one more launch, before the choice (it rewrites the rows)
             self.ops.decode_rules(logits, V, st.seq, st.seq_len, st.rule_pen, st.rule_ngram, st.rule_min_left, tok=st.tok, live=kw.get("live"),
@@ -2909,8 +2922,10 @@ class LeopardEngine:
     # ------------------------------------------------------------------------------------------------
     BEAMS_LO4 = "served"               # precision "lo4": the pair step serves B <= 8, and num_beams <= 8 always
 
-    def _set_beams(self, st, K: int, eos, row0: int, max_new_tokens: int) -> None:
-        """Make ``st`` the state of a beam search of K = st.B beams whose slots agree on rows [0, row0)."""
+    def _set_beams(self, st, K: int, eos, row0: int, max_new_tokens: int, rules: Optional[LogitsRules] = None,
+                   prompt: Sequence[int] = ()) -> None:
+        """Make ``st`` the state of a beam search of K = st.B beams whose slots agree on rows [0, row0).  With ``rules`` every slot's id
+        list starts as ``prompt`` and the step's tail is lmi_beam_step_rules + the id reorder (one more captured graph of the state)."""
         ops, dev = self.ops, self.device
         if st.beam_walk is None:
             st.beam_score = torch.zeros(ops.MAX_BEAMS, dtype=torch.float32, device=dev)
@@ -2926,7 +2941,17 @@ class LeopardEngine:
         st.beams, st.sampling = K, False
         st.beam_max_rows = (max_new_tokens + 255) // 256 * 256
         self._set_logprobs(st, None)
-        self._set_rules(st, None)
+        self._set_rules(st, rules, eos)
+        if rules is not None:
+            if st.seq.shape[1] % 4 or st.seq.data_ptr() % 16:
+                raise NotImplementedError(f"generate_beams: rules need id lists of a multiple of four ids (this state: {st.seq.shape[1]})")
+            if st.beam_id_ptr is None:
+                st.beam_id_ptr = torch.tensor([st.seq.data_ptr()], dtype=torch.int64).to(dev)
+                st.beam_id_chunks = torch.zeros(2, dtype=torch.int32, device=dev)
+            for j in range(K):
+                self._fill_rules(st, j, prompt, rules)
+            n = len(prompt)
+            st.beam_id_chunks.copy_(torch.tensor([n // 4, (n + max_new_tokens + 3) // 4], dtype=torch.int32))
         ids = sorted(eos)
         st.beam_eos.copy_(torch.tensor(ids + [-1] * (ops.BEAM_MAX_EOS - len(ids)), dtype=torch.int64))
         st.beam_score.zero_(); st.beam_parent.zero_()
@@ -2936,12 +2961,16 @@ class LeopardEngine:
     @torch.no_grad()
     def generate_beams(self, input_ids: torch.Tensor, tiles: Optional[torch.Tensor], num_beams: int, max_new_tokens: int = 128,
                        eos_token_id: Sequence[int] = (128001, 128009), length_penalty: float = 1.0, early_stopping=False,
-                       num_return_sequences: int = 1, decode: str = "shared") -> BeamOutput:
+                       num_return_sequences: int = 1, decode: str = "shared", rules: Optional[LogitsRules] = None) -> BeamOutput:
         """Beam search with ``num_beams`` = K beams (1 .. 8): transformers' ``generate(num_beams=K, do_sample=False)`` — its candidate
         selection, its finished-hypothesis bookkeeping, ``length_penalty``, the three ``early_stopping`` values (False, True, "never") and
         ``num_return_sequences`` <= K.  Among EXACT ties of the accumulated log-probability, which torch.topk leaves open, the order here
         is beam ascending, then id ascending.  ``suppress_tokens`` applies as in HF's processors: the log-probabilities are those of the
-        raw row and a suppressed id is never a candidate.
+        raw row and a suppressed id is never a candidate.  ``rules``: repetition penalty / no-repeat n-gram ban / min_new_tokens as
+        transformers applies them in beam search — to the log-softmax scores of every beam, before its accumulated score is added, each
+        beam judged against ``input_ids`` (as passed) + its own tokens (lmi_beam_step_rules; the id lists follow the beams); refused as
+        ``generate(rules=)`` refuses.  K = 1 with a repetition penalty is NOT greedy ``generate(rules=)``: beams penalise logit - lse, greedy
+        penalises the logit (HF's behaviour too).
         One prefill of the prompt into a cache of P rows; the first K beams come from its last logits row; the steps run on a pooled decode
         state of K slots, one captured step per token.  ``decode`` = "shared" (the default): the prompt's K / V rows are stored ONCE in the
         state and read once per step for all beams (lmi_attn_decode_shared), the slots hold the generated rows only — needs what
@@ -2963,6 +2992,7 @@ class LeopardEngine:
             raise ValueError(f"{what}: max_new_tokens must be at least 1, got {max_new_tokens!r}")
         if early_stopping not in (False, True, "never"):
             raise ValueError(f"{what}: early_stopping must be False, True or 'never', got {early_stopping!r}")
+        rules = self._rules_arg(what, rules, None, eos_token_id)
         V = self.cfg.text_config.vocab_size
         eos = set(int(e) for e in eos_token_id if 0 <= int(e) < V)
         if len(eos) > ops.BEAM_MAX_EOS or len(eos) > self.MAX_EOS:
@@ -3001,7 +3031,8 @@ class LeopardEngine:
                 self._load_rows([(prefix, 0, P)], st.k, st.v, j * st.capacity)
             row0 = P
         del prefix
-        self._set_beams(st, K, eos, row0, T)
+        prompt = [int(t) for t in ids.reshape(-1).tolist()]
+        self._set_beams(st, K, eos, row0, T, rules, prompt)
         st.pos.fill_(P); st.k_len.fill_(row0 + 1)
         # the first token: the same entry, run eagerly on the ONE prefill row (score 0, K outputs) — HF's initial scores [0, -1e9, ..]
         row = res.logits_last.reshape(1, -1).float()
@@ -3009,15 +3040,21 @@ class LeopardEngine:
             pad = torch.zeros(1, (row.shape[1] + 3) // 4 * 4, dtype=torch.float32, device=row.device)
             pad[:, :row.shape[1]] = row
             row = pad
-        ops.beam_step(row, min(V, row.shape[1]), K, st.beam_eos, st.beam_score, st.tok, st.beam_parent, st.beam_walk,
-                      *(t[:1] for t in st.beam_rows), suppress=self.suppress_tokens)
+        if rules is None:
+            ops.beam_step(row, min(V, row.shape[1]), K, st.beam_eos, st.beam_score, st.tok, st.beam_parent, st.beam_walk,
+                          *(t[:1] for t in st.beam_rows), suppress=self.suppress_tokens)
+        else:                                                         # nothing appended, eos banned when min_new_tokens > 0, the row untouched
+            dev = self.device
+            ints = torch.tensor([len(prompt), int(rules.no_repeat_ngram_size), int(rules.min_new_tokens)], dtype=torch.int32).to(dev)
+            ops.beam_step_rules(row, min(V, row.shape[1]), K, st.beam_eos, st.beam_score, st.tok, st.beam_parent, st.beam_walk,
+                                *(t[:1] for t in st.beam_rows), st.seq[:1], ints[0:1], st.rule_pen[:1], ints[1:2], ints[2:3],
+                                suppress=self.suppress_tokens)
         search = BeamSearch(K, T, length_penalty, early_stopping, int(num_return_sequences))
         try:
             while search.step(decode_walk(st.beam_walk.cpu().numpy())):
                 self._batch_decode_run(st)
         finally:
-            st.beams = 0                                              # the pooled state serves the other calls again, whatever happened
-        prompt = [int(t) for t in ids.reshape(-1).tolist()]
+            st.beams, st.rules = 0, False                             # the pooled state serves the other calls again, whatever happened
         best = search.results()
         return BeamOutput(sequences=[torch.tensor([prompt + seq], dtype=torch.int64, device=input_ids.device) for _, seq in best],
                           scores=[float(sc) for sc, _ in best])

@@ -296,13 +296,17 @@ class Idefics2ForConditionalGeneration:
 
     @torch.no_grad()
     def generate_beams(self, input_ids, pixel_values=None, num_beams=None, max_new_tokens: int = 128, eos_token_id=None, length_penalty=None,
-                       early_stopping=None, num_return_sequences: int = 1, pixel_attention_mask=None, attention_mask=None, **unused):
+                       early_stopping=None, num_return_sequences: int = 1, pixel_attention_mask=None, attention_mask=None,
+                       repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, **unused):
         """Beam search (HF's ``generate(num_beams=K, do_sample=False)``: LeopardEngine.generate_beams) with ``decode`` = "copy": every beam's
-        slot holds the prompt rows, which is what the sliding window of this model's decoder runs on.  ``num_beams`` / ``length_penalty``
+        slot holds the prompt rows, which is what the sliding window of this model's decoder runs on.  ``repetition_penalty`` /
+        ``no_repeat_ngram_size`` / ``min_new_tokens``: HF's logits processors on every beam's log-softmax scores (call arguments over
+        generation_config.json over "off").  ``num_beams`` / ``length_penalty``
         / ``early_stopping`` left unset take generation_config.json's value, else HF's default (1, 1.0, False); ``bad_words_ids`` are never
         candidates.  Returns the best sequence [1, n], or the list of the ``num_return_sequences`` best, best first."""
         sampling.warn_unsupported("generate_beams", unused)
         K, lp, es = sampling.resolve_beams(self.beam_defaults, num_beams, length_penalty, early_stopping)
+        rules = sampling.resolve_rules(self.generation_defaults, repetition_penalty, no_repeat_ngram_size, min_new_tokens)
         if input_ids.shape[0] != 1:
             raise NotImplementedError("batch 1 per call, as in the reference script (IDEF:88-97)")
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
@@ -311,6 +315,6 @@ class Idefics2ForConditionalGeneration:
                                                                      self.config.vision_config.patch_size)
         eos = self.eos_token_id if eos_token_id is None else (tuple(eos_token_id) if isinstance(eos_token_id, (list, tuple)) else (int(eos_token_id),))
         out = self.engine.generate_beams(input_ids.reshape(1, -1).to(self.device), images, K, max_new_tokens=max_new_tokens, eos_token_id=eos,
-                                         length_penalty=lp, early_stopping=es, num_return_sequences=num_return_sequences, decode="copy")
-        self.last_decoding = sampling.describe_beams(K, lp, es)
+                                         length_penalty=lp, early_stopping=es, num_return_sequences=num_return_sequences, decode="copy", rules=rules)
+        self.last_decoding = sampling.describe_beams(K, lp, es) + ("" if rules is None else " + " + rules.describe())
         return sampling.beam_outputs(out, num_return_sequences, input_ids.device)

@@ -568,6 +568,44 @@ class Ops:
                                            _ptr(eos), K, _ptr(score), _ptr(tok), _ptr(parent), _ptr(walk), _ptr(row_lse), _ptr(row_id), _ptr(row_lp),
                                            _ptr(row_eos_lp), _ptr(pos), _ptr(k_len), _ptr(rows_held), self._stream(logits)))
 
+    def beam_step_rules(self, logits, vocab, num_beams, eos, score, tok, parent, walk, row_lse, row_id, row_lp, row_eos_lp, seq, seq_len, penalty,
+                        ngram, min_left, append=None, suppress=None, pos=None, k_len=None, rows_held=None):
+        """lmi_beam_step_rules: ``beam_step`` with the logits processors of ``decode_rules`` applied to logit - lse of every row, before the
+        beam scores are added (HF's order in beam search): ``append[b]`` (int64, None: no append; may be ``tok``) joins ``seq[b]``, then the
+        repetition penalty ``penalty[b]``, the n-gram ban ``ngram[b]`` and — while ``min_left[b]`` > 0, then decremented — the ban of the
+        ``eos`` ids.  seq int32 [>= n_rows, seq_cap]; seq_len / ngram / min_left int32 and penalty fp32 [>= n_rows]; the rest as ``beam_step``.
+        The id lists follow the beams by ``beam_reorder`` over ``seq`` (16-byte rows of four ids)."""
+        K = int(num_beams)
+        if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+            raise TypeError(f"leopard_amd: beam_step_rules reads fp32 logits rows [n_rows, ld], got {logits.dtype} {tuple(logits.shape)}")
+        n = logits.shape[0]
+        if not 1 <= K <= self.MAX_BEAMS or n not in (1, K):
+            raise ValueError(f"leopard_amd: beam_step_rules num_beams must be in [1, {self.MAX_BEAMS}] and n_rows 1 or num_beams, got {K} and {n} rows")
+        if eos.dtype != torch.int64 or eos.numel() != self.BEAM_MAX_EOS or not eos.is_contiguous():
+            raise TypeError(f"leopard_amd: beam_step_rules eos must be a contiguous int64 [{self.BEAM_MAX_EOS}], got {eos.dtype} [{eos.numel()}]")
+        if suppress is not None and suppress.dtype != torch.int64:
+            raise TypeError(f"leopard_amd: beam_step_rules suppress must be int64, got {suppress.dtype}")
+        if seq.dtype != torch.int32 or seq.dim() != 2 or seq.shape[0] < n or seq.shape[1] < 1 or not seq.is_contiguous():
+            raise TypeError(f"leopard_amd: beam_step_rules seq must be a contiguous int32 [>= {n}, seq_cap], got {seq.dtype} {tuple(seq.shape)}")
+        for name, t, dt, need in (("score", score, torch.float32, max(n, K)), ("tok", tok, torch.int64, K), ("parent", parent, torch.int32, K),
+                                  ("walk", walk, torch.int32, self.BEAM_WALK_WORDS), ("row_lse", row_lse, torch.float32, n),
+                                  ("row_id", row_id, torch.int32, n * self.MAX_BEAMS), ("row_lp", row_lp, torch.float32, n * self.MAX_BEAMS),
+                                  ("row_eos_lp", row_eos_lp, torch.float32, n * self.BEAM_MAX_EOS), ("pos", pos, torch.int32, K),
+                                  ("k_len", k_len, torch.int32, K), ("rows_held", rows_held, torch.int32, 1), ("seq_len", seq_len, torch.int32, n),
+                                  ("penalty", penalty, torch.float32, n), ("ngram", ngram, torch.int32, n), ("min_left", min_left, torch.int32, n),
+                                  ("append", append, torch.int64, n)):
+            if t is not None and (t.dtype != dt or t.numel() < need or not t.is_contiguous()):
+                raise TypeError(f"leopard_amd: beam_step_rules {name} must be a contiguous {dt} with >= {need} entries, got {t.dtype} [{t.numel()}]")
+        if seq_len is None or penalty is None or ngram is None or min_left is None:
+            raise TypeError("leopard_amd: beam_step_rules needs seq_len, penalty, ngram and min_left")
+        if int(vocab) > self.RULES_MAX_VOCAB:
+            raise ValueError(f"leopard_amd: beam_step_rules vocab {int(vocab)} exceeds {self.RULES_MAX_VOCAB}")
+        self._check(self.lib.lmi_beam_step_rules(_ptr(logits), n, int(vocab), logits.stride(0), _ptr(suppress),
+                                                 0 if suppress is None else suppress.numel(), _ptr(eos), K, _ptr(score), _ptr(tok), _ptr(parent),
+                                                 _ptr(walk), _ptr(row_lse), _ptr(row_id), _ptr(row_lp), _ptr(row_eos_lp), _ptr(pos), _ptr(k_len),
+                                                 _ptr(rows_held), _ptr(append), _ptr(seq), _ptr(seq_len), seq.shape[1], _ptr(penalty), _ptr(ngram),
+                                                 _ptr(min_left), self._stream(logits)))
+
     def beam_reorder(self, ptrs, parent, num_beams, row0, rows_held, row_bytes, slot_rows, max_rows):
         """lmi_beam_reorder: slot b of each of the tensors whose base pointers are in ``ptrs`` (int64 [n_tensors] on the device; num_beams
         slots of ``slot_rows`` contiguous rows of ``row_bytes`` bytes each) takes rows [row0[0], rows_held[0]) of slot parent[b], in place.
