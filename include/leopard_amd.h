@@ -453,6 +453,21 @@ int lmi_rope_qkv_skinny(const void* Wqkv_rope, const void* X, void* qkv, int M, 
                         int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all, const float* sin_all,
                         void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, int dtype, void* stream);
 
+/* lmi_gemm_skinny_ex for up to 64 rows (M <= 64; everything else as there: the four epilogues, producer and consumer of the folded RMSNorm,
+ * the three weight layouts).  Row m holds exactly the bits lmi_gemm_skinny_ex gives it in any launch of at most 16 rows that contains it — the
+ * k-steps, their split over the eight waves and every summation order are the same — so a sequence decodes to the same tokens whatever the
+ * width of the step it rides in.  Up to 32 rows a workgroup owns what it owns there; above, 32 weight rows under every epilogue, so that
+ * the batch rows every workgroup reads from L2 stay below twice the weight stream. */
+int lmi_gemm_skinny_wide(const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, int packed,
+                         const float* rowsq_in, int rowsq_parts, int norm_dim, float norm_eps, void* norm_out, int ld_norm, const float* norm_gamma,
+                         float* rowsq_out, int dtype, void* stream);
+
+/* lmi_rope_qkv_skinny for up to 64 rows (M <= 64), row for row the same bits in qkv and in the appended K / V rows.  There is no row_bias
+ * form: shared-prefix decode keeps its own limit. */
+int lmi_rope_qkv_skinny_wide(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,
+                             int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all, const float* sin_all,
+                             void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, int dtype, void* stream);
+
 /* Decode precision mode (round 6; LeopardEngine.precision = "lo4" / "split" also covers the decode branch, EVAL:291-320): every operand of a
  * decode-step projection is handed over as a PAIR of 16-bit rows — T(x) and T(x - T(x)), rows m and m + M of a [2 M, K] buffer (2 M <= 16) —
  * and both products land in the same fp32 sums: the operand is seen to ~22 bits at no extra weight traffic (the step is bound by the weight

@@ -23,7 +23,7 @@ import torch
 
 from .checkpoint import CheckpointSource, load_config
 from .config import LeopardConfig
-from .engine import KVCache, LeopardEngine
+from .engine import DecodeBatchLimitOption, KVCache, LeopardEngine
 from .ops import Ops
 from .weights import EngineWeights
 from . import sampling
@@ -55,7 +55,7 @@ def resolve_precision(requested_dtype, compute_dtype, precision: Optional[str] =
     return "fast" if (tp_size > 1 and mode == "split") else mode
 
 
-class LeopardForConditionalGeneration:
+class LeopardForConditionalGeneration(DecodeBatchLimitOption):
     def __init__(self, config: LeopardConfig, source_factory, compute_dtype=torch.float16, ops: Optional[Ops] = None,
                  torch_dtype=torch.float32, precision: Optional[str] = None, tp_rank: int = 0, tp_size: int = 1):
         self.config = config
@@ -74,14 +74,17 @@ class LeopardForConditionalGeneration:
     # ---- loading ---------------------------------------------------------------------------------------------
     @classmethod
     def from_pretrained(cls, path: str, torch_dtype=torch.float32, compute_dtype=torch.float16, ops: Optional[Ops] = None,
-                        precision: Optional[str] = None, tp_rank: int = 0, tp_size: int = 1):
-        """``precision``: see resolve_precision.  ``tp_size`` > 1 (SURVEY.md 8 f1 "optional TP pre-sharding on load"): this process holds
+                        precision: Optional[str] = None, tp_rank: int = 0, tp_size: int = 1, decode_batch_limit: Optional[int] = None):
+        """``precision``: see resolve_precision.  ``decode_batch_limit`` (also a settable attribute): the most sequences generate_stream /
+        generate_batch decode in one step (LeopardEngine.decode_batch_limit; default 16).  ``tp_size`` > 1 (SURVEY.md 8 f1 "optional TP pre-sharding on load"): this process holds
         tensor-parallel shard ``tp_rank`` of the LLM — the checkpoint's tensors are sliced while they stream to the device
         (EngineWeights.build) — and needs an initialised process group of that size (leopard_amd.dist.init) by the time ``.to(device)`` runs."""
         cfg = load_config(path)
         m = cls(cfg, lambda dev, dt: CheckpointSource(path, dev, dt), compute_dtype, ops, torch_dtype=torch_dtype, precision=precision,
                 tp_rank=tp_rank, tp_size=tp_size)
         m.generation_defaults, m.beam_defaults = sampling.read_generation_defaults(path)
+        if decode_batch_limit is not None:
+            m.decode_batch_limit = decode_batch_limit
         return m
 
     def eval(self):
@@ -104,6 +107,7 @@ class LeopardForConditionalGeneration:
                 # run fast / lo4 (resolve_precision's rule for an explicit "split" request)
                 self.precision = "split" if self.tp_size == 1 else "fast"
             self._engine.precision = self.precision
+            self._apply_decode_batch_limit()
             self.device = device
         return self
 

@@ -663,6 +663,33 @@ int skinny_impl(const void* W, const void* X, void* out, int M, int N, int K, in
     return check_launch("lmi_gemm_skinny");
 }
 
+// the wide form (csrc/skinny.h skinny_wide_kernel): two column blocks up to 32 rows, four above; 32 weight rows per workgroup at four
+template <typename T, int LAYOUT, int MB>
+int skinny_wide_launch(const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, void* stream,
+                       const RopeEpi& rp, const SkinnyNorm& nm) {
+    const bool pair = epilogue == LMI_SKINNY_SWIGLU || epilogue == 4;
+    const int units = pair ? N / 32 : (MB == 4 ? (N / 16 + 1) / 2 : N / 16);
+#define LMI_SK(E) LMI_LAUNCH((skinny_wide_kernel<T, E, LAYOUT, MB>), dim3(units), dim3(512), 0, stream, (const T*)W, (const T*)X, out, M, N, K, ldw, ldx, ldo, rp, nm)
+    switch (epilogue) {
+        case LMI_SKINNY_STORE: LMI_SK(SK_STORE_T); break;
+        case LMI_SKINNY_RESIDUAL: LMI_SK(SK_RESID_F32); break;
+        case LMI_SKINNY_SWIGLU: LMI_SK(SK_SWIGLU_T); break;
+        case 4: LMI_SK(SK_QKV_ROPE_T); break;                        // lmi_rope_qkv_skinny_wide only
+        default: LMI_SK(SK_STORE_F32); break;
+    }
+#undef LMI_SK
+    return check_launch("lmi_gemm_skinny_wide");
+}
+
+// one dispatch for every skinny entry: wide = 0 -> skinny_gemm_kernel (M <= 16), wide = 1 -> skinny_wide_kernel (M <= 64)
+template <typename T, int LAYOUT>
+int skinny_any(int wide, const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, void* stream,
+               const RopeEpi& rp, const SkinnyNorm& nm) {
+    if (!wide) return skinny_impl<T, LAYOUT>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, rp, nm);
+    if (M <= 32) return skinny_wide_launch<T, LAYOUT, 2>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, rp, nm);
+    return skinny_wide_launch<T, LAYOUT, 4>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, rp, nm);
+}
+
 // the folded-norm arguments of lmi_gemm_skinny_ex / lmi_rope_qkv_skinny, checked
 int skinny_norm_args(const char* who, SkinnyNorm& nm, int M, int N, int epilogue, const float* rowsq_in, int rowsq_parts, int norm_dim, float norm_eps,
                      void* norm_out, int ld_norm, const float* norm_gamma, float* rowsq_out) {
@@ -1575,12 +1602,13 @@ int lmi_attn_prefix_rows(const void* q, const void* k_prefix, const void* v_pref
 
 static int gemm_skinny_entry(const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, int packed,
                              const float* rowsq_in, int rowsq_parts, int norm_dim, float norm_eps, void* norm_out, int ld_norm, const float* norm_gamma,
-                             float* rowsq_out, int dtype, void* stream, int hl) {
+                             float* rowsq_out, int dtype, void* stream, int hl, int wide = 0) {
+    const int max_m = wide ? 64 : 16;
     if (!W || !X || !out) return fail(LMI_EINVAL, "lmi_gemm_skinny: null pointer");
     if (hl && 2 * M > 16) return fail(LMI_EINVAL, "lmi_gemm_skinny_hl: the hi + lo row pairs need 2 M <= 16 (M = %d)", M);
-    if (M < 0 || M > 16 || N <= 0 || K <= 0 || (K % 128) || epilogue < LMI_SKINNY_STORE || epilogue > LMI_SKINNY_STORE_F32 ||
+    if (M < 0 || M > max_m || N <= 0 || K <= 0 || (K % 128) || epilogue < LMI_SKINNY_STORE || epilogue > LMI_SKINNY_STORE_F32 ||
         (N % (epilogue == LMI_SKINNY_SWIGLU ? 64 : 16)))
-        return fail(LMI_EINVAL, "lmi_gemm_skinny: need M <= 16, K %% 128 == 0, N %% 16 == 0 (SwiGLU: N %% 64 == 0) (M=%d N=%d K=%d)", M, N, K);
+        return fail(LMI_EINVAL, "lmi_gemm_skinny: need M <= %d, K %% 128 == 0, N %% 16 == 0 (SwiGLU: N %% 64 == 0) (M=%d N=%d K=%d)", max_m, M, N, K);
     if ((ldw & 7) || (ldx & 7) || ldw < K || ldx < K || (packed && ldw != K) || !aligned16(W) || !aligned16(X) ||
         ((epilogue == LMI_SKINNY_RESIDUAL || epilogue == LMI_SKINNY_STORE_F32) ? !aligned16(out) && ((uintptr_t)out & 3) : ((uintptr_t)out & 1)))
         return fail(LMI_EINVAL, "lmi_gemm_skinny: rows must be 16-byte aligned (ldw, ldx multiples of 8 and >= K)");
@@ -1593,13 +1621,13 @@ static int gemm_skinny_entry(const void* W, const void* X, void* out, int M, int
     nm.hl = hl ? 1 : 0;
     if (M == 0) return LMI_OK;
     if (packed)
-        LMI_DISPATCH_T(dtype, (skinny_impl<f16_t, 1>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)),
-                       (skinny_impl<bf16_t, 1>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)));
+        LMI_DISPATCH_T(dtype, (skinny_any<f16_t, 1>(wide, W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)),
+                       (skinny_any<bf16_t, 1>(wide, W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)));
     if (g_skinny_coalesce.load())
-        LMI_DISPATCH_T(dtype, (skinny_impl<f16_t, 2>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)),
-                       (skinny_impl<bf16_t, 2>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)));
-    LMI_DISPATCH_T(dtype, (skinny_impl<f16_t, 0>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)),
-                   (skinny_impl<bf16_t, 0>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)));
+        LMI_DISPATCH_T(dtype, (skinny_any<f16_t, 2>(wide, W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)),
+                       (skinny_any<bf16_t, 2>(wide, W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)));
+    LMI_DISPATCH_T(dtype, (skinny_any<f16_t, 0>(wide, W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)),
+                   (skinny_any<bf16_t, 0>(wide, W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, RopeEpi(), nm)));
 }
 
 int lmi_attn_decode_fwd_hl(const void* q, const void* k, const void* v, void* out, const int* cu_seqlens_q, const int* cu_seqlens_k,
@@ -1638,17 +1666,25 @@ int lmi_gemm_skinny(const void* W, const void* X, void* out, int M, int N, int K
     return lmi_gemm_skinny_ex(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, packed, nullptr, 0, 0, 0.f, nullptr, 0, nullptr, nullptr, dtype, stream);
 }
 
+int lmi_gemm_skinny_wide(const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, int packed,
+                         const float* rowsq_in, int rowsq_parts, int norm_dim, float norm_eps, void* norm_out, int ld_norm, const float* norm_gamma,
+                         float* rowsq_out, int dtype, void* stream) {
+    return gemm_skinny_entry(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, packed, rowsq_in, rowsq_parts, norm_dim, norm_eps, norm_out, ld_norm, norm_gamma,
+                             rowsq_out, dtype, stream, 0, 1);
+}
+
 static int rope_qkv_skinny_entry(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,
                                  int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all, const float* sin_all,
                                  void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, int dtype, void* stream, int hl,
-                                 const int* row_bias_dev = nullptr) {
+                                 const int* row_bias_dev = nullptr, int wide = 0) {
+    const int max_m = wide ? 64 : 16;
     if (hl && 2 * M > 16) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny_hl: the hi + lo row pairs need 2 M <= 16 (M = %d)", M);
     if (!Wqkv_rope || !X || !qkv || !cos_all || !sin_all || !k_cache || !v_cache || !pos_rows_dev) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny: null pointer");
     if (head_dim != 128) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny: head_dim %d (only 128)", head_dim);
     const int N = (n_q_heads + 2 * n_kv_heads) * head_dim;
-    if (M < 0 || M > 16 || n_q_heads <= 0 || n_kv_heads <= 0 || K <= 0 || (K % 128) || (ldw & 7) || (ldx & 7) || ldw < K || ldx < K || (packed && ldw != K) ||
+    if (M < 0 || M > max_m || n_q_heads <= 0 || n_kv_heads <= 0 || K <= 0 || (K % 128) || (ldw & 7) || (ldx & 7) || ldw < K || ldx < K || (packed && ldw != K) ||
         (ld_cache & 7) || cache_stride <= 0 || ldo < N || !aligned16(Wqkv_rope) || !aligned16(X))
-        return fail(LMI_EINVAL, "lmi_rope_qkv_skinny: bad argument (M <= 16, K %% 128 == 0, 16-byte aligned rows)");
+        return fail(LMI_EINVAL, "lmi_rope_qkv_skinny: bad argument (M <= %d, K %% 128 == 0, 16-byte aligned rows)", max_m);
     SkinnyNorm nm;
     if (int rc = skinny_norm_args("lmi_rope_qkv_skinny", nm, M, N, 4, rowsq_in, rowsq_parts, K, norm_eps, nullptr, 0, nullptr, nullptr)) return rc;
     nm.hl = hl ? 1 : 0;
@@ -1657,13 +1693,13 @@ static int rope_qkv_skinny_entry(const void* Wqkv_rope, const void* X, void* qkv
     rp.cos_all = cos_all; rp.sin_all = sin_all; rp.pos = pos_rows_dev; rp.k_cache = k_cache; rp.v_cache = v_cache; rp.ld_cache = ld_cache;
     rp.cache_stride = (long)cache_stride; rp.rope_q = n_q_heads * head_dim; rp.rope_k = n_kv_heads * head_dim; rp.row_bias = row_bias_dev;
     if (packed)
-        LMI_DISPATCH_T(dtype, (skinny_impl<f16_t, 1>(Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)),
-                       (skinny_impl<bf16_t, 1>(Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)));
+        LMI_DISPATCH_T(dtype, (skinny_any<f16_t, 1>(wide, Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)),
+                       (skinny_any<bf16_t, 1>(wide, Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)));
     if (g_skinny_coalesce.load())
-        LMI_DISPATCH_T(dtype, (skinny_impl<f16_t, 2>(Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)),
-                       (skinny_impl<bf16_t, 2>(Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)));
-    LMI_DISPATCH_T(dtype, (skinny_impl<f16_t, 0>(Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)),
-                   (skinny_impl<bf16_t, 0>(Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)));
+        LMI_DISPATCH_T(dtype, (skinny_any<f16_t, 2>(wide, Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)),
+                       (skinny_any<bf16_t, 2>(wide, Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)));
+    LMI_DISPATCH_T(dtype, (skinny_any<f16_t, 0>(wide, Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)),
+                   (skinny_any<bf16_t, 0>(wide, Wqkv_rope, X, qkv, M, N, K, ldw, ldx, ldo, 4, stream, rp, nm)));
 }
 
 int lmi_rope_qkv_skinny(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,
@@ -1671,6 +1707,13 @@ int lmi_rope_qkv_skinny(const void* Wqkv_rope, const void* X, void* qkv, int M, 
                         void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, int dtype, void* stream) {
     return rope_qkv_skinny_entry(Wqkv_rope, X, qkv, M, n_q_heads, n_kv_heads, head_dim, K, ldw, ldx, ldo, packed, rowsq_in, rowsq_parts, norm_eps, cos_all,
                                  sin_all, k_cache, v_cache, ld_cache, cache_stride, pos_rows_dev, dtype, stream, 0);
+}
+
+int lmi_rope_qkv_skinny_wide(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,
+                             int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all, const float* sin_all,
+                             void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, int dtype, void* stream) {
+    return rope_qkv_skinny_entry(Wqkv_rope, X, qkv, M, n_q_heads, n_kv_heads, head_dim, K, ldw, ldx, ldo, packed, rowsq_in, rowsq_parts, norm_eps, cos_all,
+                                 sin_all, k_cache, v_cache, ld_cache, cache_stride, pos_rows_dev, dtype, stream, 0, nullptr, 1);
 }
 
 int lmi_rope_qkv_skinny_hl(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,

@@ -227,6 +227,212 @@ __global__ void __launch_bounds__(512) skinny_gemm_kernel(const T* W, const T* X
 }
 
 // ------------------------------------------------------------------------------------------------
+// The wide form: M <= 16 MB batch rows (MB = 2 or 4 column blocks of the 16x16x32 MFMA), every epilogue of skinny_gemm_kernel but the hl
+// pairs.  Row m gets the BITS skinny_gemm_kernel gives it in any launch of at most 16 rows that holds it: an MFMA output column depends on
+// its own X row only, and everything that orders a row's sums is kept — 128-element k-steps, step s on wave s % 8, chunks c = 0..3 within a
+// step, the w = 0..7 sum of the partial tiles, the 32-lane rstd reduction of the consumer, the n = 0..15 column sum of the producer.
+// What differs is what a workgroup owns and how X is held:
+//   * MB = 4 owns TWO 16-row weight blocks under every epilogue (the paired ones already do; the plain ones take blocks 2 u and 2 u + 1,
+//     the second one dead when N / 16 is odd): every workgroup reads all of X from L2, so at 16 weight rows and 64 batch rows X would be
+//     4x the weight stream (~22 TB/s of L2 at the 5.5 TB/s the weights arrive with, more than rows shared by every workgroup deliver);
+//     32 rows halve it.  MB = 2 keeps skinny_gemm_kernel's ownership (X = 2x the weights at 16 rows, 1x at 32).
+//   * weights keep their 3 (one block) or 2 (two blocks) k-steps of loads in flight; X holds ONE step — 16 MB registers — and chunk c is
+//     re-requested for the next step as soon as this step's MFMAs of chunk c are issued.  X comes from L2 and a wave needs a step only
+//     once per weight-stream round, so one step ahead is enough; two steps of four column blocks would not fit beside the weights.
+//     Registers per lane: 16 NW DEPTH + 16 MB + 4 NW MB = 88 (MB 2, one block), 112 (MB 2, pair), 160 (MB 4) before addresses; compiled:
+//     106 - 114, 137 - 148 and 200 - 204, no scratch.  Holding the MB = 2 pairs to 128 (two workgroups per CU, as the one-block forms have)
+//     makes them spill 12 - 18 registers, so they run one workgroup per CU like MB = 4.
+//   * the 8 partial tiles of ONE column block meet in LDS at a time (16 KiB as before), column block after column block.
+// ------------------------------------------------------------------------------------------------
+template <typename T, int EPI, int LAYOUT, int MB>
+__global__ void __launch_bounds__(512) skinny_wide_kernel(const T* W, const T* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, RopeEpi rp,
+                                                          SkinnyNorm nm) {
+    typedef typename vec_of<T>::x8 T8;
+    constexpr bool PACKED = (LAYOUT == 1), COAL = (LAYOUT == 2);
+    constexpr bool PAIR = (EPI == SK_SWIGLU_T || EPI == SK_QKV_ROPE_T);
+    constexpr int NW = (PAIR || MB == 4) ? 2 : 1;                  // weight row blocks per workgroup
+    constexpr int BROWS = PAIR ? 32 : 16;                          // rows from block 0 to block 1: the pair partner / the next block
+    constexpr int DEPTH = NW == 2 ? 2 : 3;                         // k-steps of WEIGHT loads in flight per wave
+    __shared__ float part[8][NW][64][4];
+    __shared__ float rstd_s[16 * MB], sq_s[NW][16][17];
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
+    const int i = lane & 15, g = lane >> 4;
+    const int unit = blockIdx.x;
+    // consumer: as skinny_gemm_kernel, once per column block (row 16 mb + (tid >> 5))
+    float ssq[MB];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) {
+        ssq[mb] = 0.f;
+        const int m = 16 * mb + (tid >> 5);
+        if (nm.rowsq_in && m < M)
+            for (int q = tid & 31; q < nm.parts_in; q += 32) ssq[mb] += nm.rowsq_in[(long)m * nm.parts_in + q];
+    }
+    const int row0 = PAIR ? (unit >> 1) * 64 + (unit & 1) * 16 : unit * 16 * NW;
+    const int live = (PAIR || (N >> 4) - unit * NW >= NW) ? NW : 1;   // blocks inside W (a dead block streams block 0 again and stores nothing)
+    const int nsteps = K >> 7;
+    const T* wrow[NW];
+#pragma unroll
+    for (int b = 0; b < NW; ++b) {
+        const int r = row0 + (b < live ? BROWS * b : 0);
+        wrow[b] = PACKED ? W + (long)(r >> 4) * nsteps * 2048 + lane * 8
+                  : COAL ? W + (long)(r + (lane >> 2)) * ldw + 8 * (lane & 3)
+                         : W + (long)(r + i) * ldw + 8 * g;
+    }
+    const int src_lane = 4 * i + g;
+    const T* xrow = X + (long)i * ldx + 8 * g;
+    const int my_steps = (nsteps - wave + 7) >> 3;                 // steps wave, wave + 8, ...
+    T8 wv[DEPTH][NW][4], xv[4][MB];
+    auto load_w = [&](int slot, int s) {
+        const int k0 = (wave + 8 * s) * 128;
+#pragma unroll
+        for (int b = 0; b < NW; ++b)
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                wv[slot][b][c] = ld_stream(PACKED ? (const T8*)(wrow[b] + (long)(wave + 8 * s) * 2048 + c * 512) : (const T8*)(wrow[b] + k0 + 32 * c));
+    };
+    auto load_x = [&](int s, int c) {
+        const int k0 = (wave + 8 * s) * 128 + 32 * c;
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb) {
+            if (i + 16 * mb < M) xv[c][mb] = *(const T8*)(xrow + (long)(16 * mb) * ldx + k0);
+            else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) xv[c][mb][e] = (T)0.0f;
+            }
+        }
+    };
+    f32x4 acc[NW][MB];
+#pragma unroll
+    for (int b = 0; b < NW; ++b)
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb) acc[b][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (my_steps > 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) load_x(0, c);
+    }
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d)
+        if (d < my_steps) load_w(d, d);
+    for (int base = 0; base < my_steps; base += DEPTH) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; ++d) {
+            const int s = base + d;
+            if (s < my_steps) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+#pragma unroll
+                    for (int b = 0; b < NW; ++b) {
+                        T8 wf = wv[d][b][c];
+                        if (COAL) {
+                            u32x4 raw = __builtin_bit_cast(u32x4, wf);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) raw[e] = (uint32_t)shfl_idx((int)raw[e], src_lane);
+                            wf = __builtin_bit_cast(T8, raw);
+                        }
+#pragma unroll
+                        for (int mb = 0; mb < MB; ++mb) acc[b][mb] = mfma16(wf, xv[c][mb], acc[b][mb]);
+                    }
+                    if (s + 1 < my_steps) load_x(s + 1, c);
+                }
+                if (s + DEPTH < my_steps) load_w(d, s + DEPTH);
+            }
+        }
+    }
+    if (nm.rowsq_in) {
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb) {
+            float q = ssq[mb];
+#pragma unroll
+            for (int msk = 16; msk >= 1; msk >>= 1) q += shfl_xor(q, msk);
+            if ((tid & 31) == 0) rstd_s[16 * mb + (tid >> 5)] = 1.0f / sqrtf(q * nm.inv_dim + nm.eps);
+        }
+    }
+    const bool producer = EPI == SK_RESID_F32 && nm.norm_out;
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) {
+        if (16 * mb < M) {                                          // uniform: a column block without a live row has nothing to finish
+#pragma unroll
+            for (int b = 0; b < NW; ++b) *(f32x4*)part[wave][b][lane] = acc[b][mb];
+            __syncthreads();
+            if (tid < 256) {
+                const int l = tid & 63, r = tid >> 6;
+                const int n = 4 * (l >> 4) + r, m = 16 * mb + (l & 15);
+                float v[NW];
+#pragma unroll
+                for (int b = 0; b < NW; ++b) {
+                    float s = part[0][b][l][r];
+#pragma unroll
+                    for (int w = 1; w < 8; ++w) s += part[w][b][l][r];
+                    v[b] = nm.rowsq_in ? s * rstd_s[m] : s;
+                }
+                if (m < M) {
+                    if (EPI == SK_QKV_ROPE_T) {                     // element for element skinny_gemm_kernel's epilogue (no row_bias form)
+                        const int c1 = row0 + n, c2 = c1 + 32;
+                        T* orow = (T*)out + (long)m * ldo;
+                        const int p = rp.pos[m];
+                        const long crow = (long)m * rp.cache_stride + p;
+                        if (c1 >= rp.rope_q + rp.rope_k) {
+                            const int vc = rp.rope_q + rp.rope_k;
+                            orow[c1] = (T)v[0];
+                            orow[c2] = (T)v[NW - 1];
+                            T* vrow = (T*)rp.v_cache + crow * rp.ld_cache - vc;
+                            vrow[c1] = (T)v[0];
+                            vrow[c2] = (T)v[NW - 1];
+                        } else {
+                            const int hbase = c1 & ~127, j = c1 & 127;
+                            const int d1 = (j >> 6) * 32 + (j & 31);
+                            const float cs = rp.cos_all[(long)p * 64 + d1], sn = rp.sin_all[(long)p * 64 + d1];
+                            const T o1 = (T)__builtin_fmaf(v[0], cs, -mul_rn(v[NW - 1], sn));
+                            const T o2 = (T)__builtin_fmaf(v[NW - 1], cs, mul_rn(v[0], sn));
+                            orow[hbase + d1] = o1;
+                            orow[hbase + d1 + 64] = o2;
+                            if (c1 >= rp.rope_q) {
+                                T* krow = (T*)rp.k_cache + crow * rp.ld_cache - rp.rope_q;
+                                krow[hbase + d1] = o1;
+                                krow[hbase + d1 + 64] = o2;
+                            }
+                        }
+                    } else if (EPI == SK_SWIGLU_T) {
+                        const float gt = v[0], up = v[NW - 1];
+                        const float y = sep_rn(gt / (1.0f + fexp(-gt)) * up);
+                        ((T*)out)[(long)m * ldo + (unit >> 1) * 32 + (unit & 1) * 16 + n] = (T)y;
+                    } else {
+#pragma unroll
+                        for (int b = 0; b < NW; ++b) {
+                            if (b < live) {
+                                const int col = row0 + 16 * b + n;
+                                if (EPI == SK_STORE_T) ((T*)out)[(long)m * ldo + col] = (T)v[b];
+                                else if (EPI == SK_STORE_F32) ((float*)out)[(long)m * ldo + col] = v[b];
+                                else {
+                                    float* xo = (float*)out + (long)m * ldo + col;
+                                    const float xn = *xo + v[b];
+                                    *xo = xn;
+                                    if (nm.norm_out) {
+                                        const float y = sep_rn(xn * nm.gamma[col]);
+                                        ((T*)nm.norm_out)[(long)m * nm.ld_norm + col] = (T)y;
+                                        sq_s[b][n][l & 15] = xn * xn;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            __syncthreads();                                        // part (and sq_s) are complete; the next column block may overwrite part
+            if (producer && tid < 16 * NW) {
+                const int b = tid >> 4, m = 16 * mb + (tid & 15);
+                if (b < live && m < M) {
+                    float q = 0.f;
+#pragma unroll
+                    for (int n = 0; n < 16; ++n) q += sq_s[b][n][tid & 15];
+                    nm.rowsq_out[(long)m * (N >> 4) + (row0 >> 4) + b] = q;
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // RoPE + KV append for the B rows of a batched decode step: row s is sequence s's next token at position pos[s] (device memory:
 // the step is graph-captured); its rotated K and its V go to row s * cache_stride + pos[s] of the pooled caches.
 // Same arithmetic per element as rope_kernel.

@@ -428,6 +428,7 @@ class LeopardEngine:
         self._gen_cache = None         # the KV cache generate() reuses (_generation_cache)
         self._stream_cache = None      # the KV cache generate_stream prefills a newcomer into before its rows move to a slot
         self._batch_states: Dict[int, DecodeState] = {}   # B -> state of the batched decode step (_batch_state)
+        self._decode_batch_limit = self.MAX_DECODE_BATCH   # decode_batch_limit: sequences per captured step of generate_stream / generate_batch
         self._skinny_pack = None       # second copy of the LLM weights in the skinny-M operand order (_skinny_weights)
         self._head_pack = None         # lm_head in the packed order (_skinny_head)
         # ONE copy of the LLM weights (default; LMI_PACK_LLM_WEIGHTS=0 / pack_llm_weights=False keep the nn.Linear layout): see pack_llm_weights
@@ -2155,6 +2156,22 @@ class LeopardEngine:
     MAX_DECODE_BATCH = 16              # rows of one lmi_gemm_skinny launch (one 16x16x32 MFMA column block)
     HIST = 8                           # continuous batching: decode steps between two host looks at the produced tokens
     MAX_EOS = 4                        # eos ids held on the device
+    WIDE_DECODE_BATCH = 64             # rows of one lmi_gemm_skinny_wide launch (four column blocks): the most decode_batch_limit admits
+
+    @property
+    def decode_batch_limit(self) -> int:
+        """The most sequences generate_stream / generate_batch decode in ONE captured step (default MAX_DECODE_BATCH).  Above 16 the step's
+        projections and head run on the wide kernels (lmi_gemm_skinny_wide, lmi_rope_qkv_skinny_wide: M <= 64), which give every row the
+        bits the 16-row kernels give it, so a request decodes to the same tokens at any width; a precision mode ("lo4" / "split") decodes
+        more than 8 sequences on the fast step, as it does 9 .. 16.  The pooled KV cache is B x capacity rows per layer, and the pools of the
+        two most recent batch sizes are kept: size the limit to the memory left beside the weights."""
+        return self._decode_batch_limit
+
+    @decode_batch_limit.setter
+    def decode_batch_limit(self, value) -> None:
+        if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= self.WIDE_DECODE_BATCH:
+            raise ValueError(f"decode_batch_limit must be an integer in 1 .. {self.WIDE_DECODE_BATCH}, got {value!r}")
+        self._decode_batch_limit = value
 
     def _batch_decode_supported(self) -> bool:
         """lmi_gemm_skinny needs K % 128 == 0 and N % 16 == 0 (gate/up: % 64); the pooled decode attention head_dim 128."""
@@ -2274,6 +2291,12 @@ class LeopardEngine:
         fold = self.skinny_fold_norm and D % 16 == 0 and all(L.qkv_w_rope is not None for L in W.llm_layers) and hd == 128
         hl = st.hl                                                    # decode precision mode: operands are [hi rows; lo rows] pairs (decode_hl)
         assert not hl or fold
+        # a wide step (decode_batch_limit > 16): launch for launch the same step on the M <= 64 entries, which give every row the bits of the
+        # 16-row kernels and have no pair and no row_bias form (decode_hl and the shared-prefix step keep their own limits)
+        wide = st.B > self.MAX_DECODE_BATCH
+        assert not wide or (not hl and st.prefix_len is None)
+        gemm, hlk = (ops.gemm_skinny_wide, {}) if wide else (ops.gemm_skinny, {"hl": hl})
+        norm = self._rmsnorm_rows32 if wide else ops.rmsnorm
         for i, L in enumerate(W.llm_layers):
             rope_fused = L.qkv_w_rope is not None and hd == 128
             qkv_w, o_w, gu_w, down_w = pk["layers"][i] if pk else (L.qkv_w_rope if rope_fused else L.qkv_w, L.o_w, L.gu_w, L.down_w)
@@ -2282,26 +2305,35 @@ class LeopardEngine:
                 ops.rmsnorm(st.x, L.in_norm, st.hf32, eps)            # the first norm in fp32, handed over as a pair
                 ops.split_rows_hl(st.hf32, st.h)
             elif not fold or i == 0:
-                ops.rmsnorm(st.x, L.in_norm, st.h, eps)
-            if rope_fused:
+                norm(st.x, L.in_norm, st.h, eps)
+            if rope_fused and wide:
+                ops.rope_qkv_skinny_wide(qkv_w, st.h, st.qkv, H, KV, hd, st.cos, st.sin, k_list[i], v_list[i], capacity, st.pos, packed,
+                                         rowsq_in=st.sq_b if fold and i > 0 else None, norm_eps=eps)
+            elif rope_fused:
                 ops.rope_qkv_skinny(qkv_w, st.h, st.qkv, H, KV, hd, st.cos, st.sin, k_list[i], v_list[i], capacity, st.pos, packed,
                                     rowsq_in=st.sq_b if fold and i > 0 else None, norm_eps=eps, hl=hl, row_bias=st.prefix_len)
             else:
-                ops.gemm_skinny(qkv_w, st.h, st.qkv, 0, packed)
+                gemm(qkv_w, st.h, st.qkv, 0, packed)
                 ops.rope_qk_rows(st.qkv, H, KV, hd, st.cos, st.sin, k_list[i], v_list[i], capacity, st.pos, row_bias=st.prefix_len)
             attend(i)
             if fold:
-                ops.gemm_skinny(o_w, st.att, st.x, 1, packed, norm_out=st.h, norm_gamma=L.post_norm, rowsq_out=st.sq_a, hl=hl)
-                ops.gemm_skinny(gu_w, st.h, st.gu, 2, packed, rowsq_in=st.sq_a, norm_dim=D, norm_eps=eps, hl=hl)
+                gemm(o_w, st.att, st.x, 1, packed, norm_out=st.h, norm_gamma=L.post_norm, rowsq_out=st.sq_a, **hlk)
+                gemm(gu_w, st.h, st.gu, 2, packed, rowsq_in=st.sq_a, norm_dim=D, norm_eps=eps, **hlk)
                 if i + 1 < n_layers:
-                    ops.gemm_skinny(down_w, st.gu, st.x, 1, packed, norm_out=st.h, norm_gamma=W.llm_layers[i + 1].in_norm, rowsq_out=st.sq_b, hl=hl)
+                    gemm(down_w, st.gu, st.x, 1, packed, norm_out=st.h, norm_gamma=W.llm_layers[i + 1].in_norm, rowsq_out=st.sq_b, **hlk)
                 else:
-                    ops.gemm_skinny(down_w, st.gu, st.x, 1, packed, hl=hl)
+                    gemm(down_w, st.gu, st.x, 1, packed, **hlk)
             else:
-                ops.gemm_skinny(o_w, st.att, st.x, 1, packed)
-                ops.rmsnorm(st.x, L.post_norm, st.h, eps)
-                ops.gemm_skinny(gu_w, st.h, st.gu, 2, packed)
-                ops.gemm_skinny(down_w, st.gu, st.x, 1, packed)
+                gemm(o_w, st.att, st.x, 1, packed)
+                norm(st.x, L.post_norm, st.h, eps)
+                gemm(gu_w, st.h, st.gu, 2, packed)
+                gemm(down_w, st.gu, st.x, 1, packed)
+
+    def _rmsnorm_rows32(self, x, gamma, out, eps) -> None:
+        """lmi_rmsnorm over the rows of a wide step, at most 32 per launch: up to 32 rows it takes its few-rows kernel, above them one
+        wave per row, which adds the squares in another order — in chunks a slot keeps the bits it has in a step of at most 16."""
+        for r0 in range(0, x.shape[0], 32):
+            self.ops.rmsnorm(x[r0:r0 + 32], gamma, out[r0:r0 + 32], eps)
 
     def _skinny_head(self):
         """lm_head in the packed order for the batched step (shared with _skinny_weights' second copy when there is one)."""
@@ -2333,6 +2365,9 @@ class LeopardEngine:
             ops.rmsnorm(st.x, W.final_norm, st.hf32, eps)
             ops.split_rows_hl(st.hf32, st.h)
             ops.gemm_skinny(self._skinny_head() if self.skinny_packed else W.lm_head, st.h, st.logits, 3, hl=True)
+        elif st.B > self.MAX_DECODE_BATCH:                            # a wide step: the final norm in chunks, the head on the M <= 64 entry
+            self._rmsnorm_rows32(st.x, W.final_norm, st.h, eps)
+            ops.gemm_skinny_wide(self._skinny_head() if self.skinny_packed else W.lm_head, st.h, st.logits, 3)
         else:
             ops.rmsnorm(st.x, W.final_norm, st.h, eps)
             ops.gemm_skinny(self._skinny_head() if self.skinny_packed else W.lm_head, st.h, st.logits, 3)
@@ -2423,7 +2458,7 @@ class LeopardEngine:
         k = self._logprobs_arg("generate_stream", logprobs)
         rules = self._rules_arg("generate_stream", rules, k, eos_token_id)
         assert self.tp_size == 1, "batched generation is a single-rank feature (replicas scale it out)"
-        B = max(1, min(int(batch_size), self.MAX_DECODE_BATCH, len(samples)))
+        B = max(1, min(int(batch_size), self.decode_batch_limit, len(samples)))
         eos = [int(e) for e in eos_token_id]
         req = (lambda i: None) if sampling is None else sampling.for_request
         if B == 1 or not self._batch_decode_supported() or len(eos) > self.MAX_EOS:
@@ -2533,11 +2568,15 @@ class LeopardEngine:
         k = self._logprobs_arg("generate_batch", logprobs)
         rules = self._rules_arg("generate_batch", rules, k, eos_token_id)
         assert self.tp_size == 1, "batched generation is a single-rank feature (replicas scale it out)"
-        if len(samples) > self.MAX_DECODE_BATCH:
-            outs = [self.generate_batch(samples[i:i + self.MAX_DECODE_BATCH], max_new_tokens, eos_token_id, sampling, _first_request + i, k, rules)
-                    for i in range(0, len(samples), self.MAX_DECODE_BATCH)]
+        # more samples than one step decodes (decode_batch_limit; 16 where the shape has no batched decode): one call per group
+        limit = self.decode_batch_limit if self._batch_decode_supported() else self.MAX_DECODE_BATCH
+        if len(samples) > limit:
+            outs = [self.generate_batch(samples[i:i + limit], max_new_tokens, eos_token_id, sampling, _first_request + i, k, rules)
+                    for i in range(0, len(samples), limit)]
             return [o for part in outs for o in part] if k is None else GenerateOutput.join(outs)
         req = (lambda i: None) if sampling is None else (lambda i: sampling.for_request(_first_request + i))
+        if len(samples) > self.MAX_DECODE_BATCH:
+            return self._generate_batch_wide(samples, max_new_tokens, eos_token_id, sampling, req, k, rules)
         if len(samples) == 1:
             ids, t = samples[0]
             one = self.generate(ids, t, max_new_tokens, eos_token_id, sampling=req(0), logprobs=k, rules=rules)
@@ -2559,6 +2598,35 @@ class LeopardEngine:
             del packed
             outs = self._greedy_loop_batch(st, prompts, first, seq_lens, max_new_tokens, eos,
                                            None if sampling is None else [req(j) for j in range(len(samples))], lpr=lpr, rules=rules)
+        return self._outputs(outs, [ids for ids, _ in samples], lpr, [len(p) for p in prompts])
+
+    def _generate_batch_wide(self, samples, max_new_tokens: int, eos_token_id, sampling, req, k, rules):
+        """generate_batch for 17 .. decode_batch_limit samples: ONE pooled decode state for all of them.  The packed prefill still runs in
+        groups of at most MAX_DECODE_BATCH samples (its workspace grows with the packed rows: 64 prompts of the C3 size would need tens of
+        GB), each group's K / V rows move to their slots of the one pool, and all samples decode together."""
+        G = self.MAX_DECODE_BATCH
+        seq_all = [self.merged_len(ids) for ids, _ in samples]
+        st = self._batch_state(len(samples), max(seq_all) + max_new_tokens)
+        prompts = [[int(t) for t in ids.reshape(-1).tolist()] for ids, _ in samples]
+        eos = set(int(e) for e in eos_token_id)
+        first: List[int] = []
+        lpr = None if k is None else []
+        for g0 in range(0, len(samples), G):
+            group = samples[g0:g0 + G]
+            x, seq_lens = self._pack_requests(group)
+            packed = KVCache(self.cfg, sum(seq_lens), self.dtype, self.device)
+            last, _ = self.llm_prefill(x, seq_lens, cache=packed)
+            f, rows = self._first_tokens(last, None if sampling is None else [req(g0 + j) for j in range(len(group))], k, rules,
+                                         prompts[g0:g0 + G], eos)
+            first += f
+            if lpr is not None:
+                lpr += rows
+            offs = [0] + [int(c) for c in np.cumsum(seq_lens)]
+            for j, S in enumerate(seq_lens):
+                self._load_rows([(packed, offs[j], S)], st.k, st.v, (g0 + j) * st.capacity)
+            del packed
+        outs = self._greedy_loop_batch(st, prompts, first, seq_all, max_new_tokens, eos,
+                                       None if sampling is None else [req(j) for j in range(len(samples))], lpr=lpr, rules=rules)
         return self._outputs(outs, [ids for ids, _ in samples], lpr, [len(p) for p in prompts])
 
     # ------------------------------------------------------------------------------------------------
@@ -3058,3 +3126,30 @@ class LeopardEngine:
         best = search.results()
         return BeamOutput(sequences=[torch.tensor([prompt + seq], dtype=torch.int64, device=input_ids.device) for _, seq in best],
                           scores=[float(sc) for sc, _ in best])
+
+
+
+class DecodeBatchLimitOption:
+    """``decode_batch_limit`` of a model object (leopard_amd.compat / idefics2_compat): kept until ``.to(device)`` builds the engine, then the
+    engine's (LeopardEngine.decode_batch_limit, which also checks the value).  The object names its engine ``_engine``."""
+    _decode_batch_limit: Optional[int] = None                       # None: the engine's default
+
+    @property
+    def decode_batch_limit(self) -> int:
+        eng = getattr(self, "_engine", None)
+        if eng is not None:
+            return eng.decode_batch_limit
+        return LeopardEngine.MAX_DECODE_BATCH if self._decode_batch_limit is None else self._decode_batch_limit
+
+    @decode_batch_limit.setter
+    def decode_batch_limit(self, value) -> None:
+        if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= LeopardEngine.WIDE_DECODE_BATCH:
+            raise ValueError(f"decode_batch_limit must be an integer in 1 .. {LeopardEngine.WIDE_DECODE_BATCH}, got {value!r}")
+        self._decode_batch_limit = value
+        if getattr(self, "_engine", None) is not None:
+            self._engine.decode_batch_limit = value
+
+    def _apply_decode_batch_limit(self) -> None:
+        """Called by ``.to`` once the engine exists."""
+        if self._decode_batch_limit is not None:
+            self._engine.decode_batch_limit = self._decode_batch_limit

@@ -170,6 +170,7 @@ def run_inference(records: List[dict], model, tokenizer, setting: str = "direct"
     for bit); without it the reference's host pipeline is used.  ``batch_size`` > 1: that many decode SLOTS are kept busy over all
     records (``model.generate_stream``: continuous batching — one captured decode step per token for all slots, a finished record's slot
     goes to the next record at once) instead of the reference's one ``generate`` per record; the rows are the same, in record order.
+    The model keeps at most ``model.decode_batch_limit`` slots (default 16; up to 64 when set — same tokens per record at any width).
     ``stats`` (dict) receives the slot occupancy.  A model without ``generate_stream`` falls back to fixed groups (``generate_batch``).
     ``logprobs`` = k (0 .. 8): the model's generate surfaces run with ``logprobs=k`` and every row additionally carries ``answer_logprob`` (the sum
     of its answer's token log-probabilities) and ``token_logprobs`` (a list); without it the rows are unchanged."""

@@ -28,6 +28,7 @@ import torch
 
 from .checkpoint import CheckpointSource
 from .config import Idefics2Config, PerceiverConfig, TextConfig, VisionConfig
+from .engine import DecodeBatchLimitOption
 from .idefics2 import Idefics2Engine, Idefics2Weights, preprocess_image_u8
 from .ops import Ops
 from . import sampling
@@ -142,7 +143,7 @@ def load_idefics2_config(path: str) -> Idefics2Config:
                           longest_edge=int(d.get("longest_edge", base.longest_edge)))
 
 
-class Idefics2ForConditionalGeneration:
+class Idefics2ForConditionalGeneration(DecodeBatchLimitOption):
     """``AutoModelForVision2Seq.from_pretrained(...)`` stand-in for the reference script: ``.to()``, ``.eval()``, ``.device``,
     ``.generate(input_ids=, attention_mask=, pixel_values=, pixel_attention_mask=, max_new_tokens=)``."""
 
@@ -166,8 +167,9 @@ class Idefics2ForConditionalGeneration:
 
     @classmethod
     def from_pretrained(cls, path: str, torch_dtype=torch.float16, ops: Optional[Ops] = None, patch_validity: str = "any",
-                        precision: Optional[str] = None, **unused):
-        """``precision`` / ``LEOPARD_AMD_PRECISION``: see leopard_amd.compat.resolve_precision.  The reference loads this model in fp16
+                        precision: Optional[str] = None, decode_batch_limit: Optional[int] = None, **unused):
+        """``precision`` / ``LEOPARD_AMD_PRECISION``: see leopard_amd.compat.resolve_precision.  ``decode_batch_limit`` (also a settable
+        attribute): the most sequences generate_stream / generate_batch decode in one step (LeopardEngine.decode_batch_limit; default 16).  The reference loads this model in fp16
         (idefics2_multiimg.py:27-28), so the default for its request is the fast fp16 schedule; a float32 request selects lo4."""
         cfg = load_idefics2_config(path)
         eos, bad = (2, 32002), None
@@ -185,6 +187,8 @@ class Idefics2ForConditionalGeneration:
         m.generation_defaults, m.beam_defaults = sampling.read_generation_defaults(path)
         from .compat import resolve_precision
         m.precision = resolve_precision(torch_dtype, dtype, precision)
+        if decode_batch_limit is not None:
+            m.decode_batch_limit = decode_batch_limit
         return m
 
     def eval(self):
@@ -203,6 +207,7 @@ class Idefics2ForConditionalGeneration:
             vocab = self.config.text_config.vocab_size
             bad = [b for b in self.bad_words_ids if 0 <= b < vocab]
             self._engine.suppress_tokens = torch.tensor(bad, dtype=torch.int64, device=device) if bad else None
+            self._apply_decode_batch_limit()
             self.device = device
         return self
 

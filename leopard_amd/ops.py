@@ -376,6 +376,30 @@ class Ops:
                                                  k_cache.stride(0), int(cache_stride), _ptr(pos_rows), _DT[w_rope.dtype], self._stream(qkv)))
         return qkv
 
+    def gemm_skinny_wide(self, w, x, out, epilogue=0, packed=None, rowsq_in=None, norm_dim=0, norm_eps=0.0, norm_out=None, norm_gamma=None,
+                         rowsq_out=None):
+        """lmi_gemm_skinny_wide: ``gemm_skinny`` for M <= 64 rows (no ``hl`` form); row m has the bits ``gemm_skinny`` gives it in any launch of
+        at most 16 rows that holds it."""
+        N, K = w.shape
+        if packed is None:
+            packed = getattr(w, "_lmi_packed", False)
+        self._check(self.lib.lmi_gemm_skinny_wide(_ptr(w), _ptr(x), _ptr(out), x.shape[0], N, K, w.stride(0), x.stride(0), out.stride(0), int(epilogue),
+                                                  int(bool(packed)), _ptr(rowsq_in), 0 if rowsq_in is None else rowsq_in.shape[1], int(norm_dim),
+                                                  float(norm_eps), _ptr(norm_out), 0 if norm_out is None else norm_out.stride(0), _ptr(norm_gamma),
+                                                  _ptr(rowsq_out), _DT[w.dtype], self._stream(out)))
+        return out
+
+    def rope_qkv_skinny_wide(self, w_rope, x, qkv, n_q_heads, n_kv_heads, head_dim, cos_all, sin_all, k_cache, v_cache, cache_stride, pos_rows,
+                             packed=None, rowsq_in=None, norm_eps=0.0):
+        """lmi_rope_qkv_skinny_wide: ``rope_qkv_skinny`` for M <= 64 rows (no ``hl`` and no ``row_bias`` form), row for row the same bits."""
+        if packed is None:
+            packed = getattr(w_rope, "_lmi_packed", False)
+        self._check(self.lib.lmi_rope_qkv_skinny_wide(
+            _ptr(w_rope), _ptr(x), _ptr(qkv), x.shape[0], n_q_heads, n_kv_heads, head_dim, w_rope.shape[1], w_rope.stride(0), x.stride(0), qkv.stride(0),
+            int(bool(packed)), _ptr(rowsq_in), 0 if rowsq_in is None else rowsq_in.shape[1], float(norm_eps), _ptr(cos_all), _ptr(sin_all),
+            _ptr(k_cache), _ptr(v_cache), k_cache.stride(0), int(cache_stride), _ptr(pos_rows), _DT[w_rope.dtype], self._stream(qkv)))
+        return qkv
+
     def llm_prefill_workspace(self, rows, hidden, n_q_heads, n_kv_heads, head_dim, ff, dtype):
         """lmi_llm_prefill_workspace_bytes -> (total bytes, [byte offset of LMI_WS_LLM_* buffer])."""
         import ctypes as C
