@@ -491,6 +491,23 @@ int lmi_attn_decode_pool_hl(const void* q, const void* k, const void* v, void* o
                             int ldq, int ldk, int ldv, int ldo, float scale, int window, void* workspace, int64_t workspace_bytes,
                             int dtype, void* stream);
 
+/* The pair entries for up to 32 pairs (1 <= M <= 32; LeopardEngine.decode_pair_limit): lmi_gemm_skinny_hl / lmi_rope_qkv_skinny_hl on the wide
+ * kernel.  Buffer layouts are those of the _hl entries above — X [2 M, K] = [T(x) rows; T(x - T(x)) rows], STORE / SWIGLU results and the
+ * producer's norm_out as rows m and m + M again (2 M rows), q | k | v rows, the K / V appends, STORE_F32, the fp32 residual stream and rowsq_out
+ * single (M rows) — so lmi_split_rows_hl and lmi_attn_decode_*_hl serve them unchanged.  All three weight layouts, the four epilogues and the
+ * RoPE one, producer and consumer of the folded RMSNorm.  Row m and its lo row hold exactly the bits the _hl entries give them in any launch of
+ * at most 8 pairs that contains the pair: the k-steps, their split over the eight waves, the sum of the hi partials, then of the lo partials,
+ * then hi + lo, rstd, the epilogue arithmetic and the lo image y - (float)T(y) are the same.  Up to 16 pairs a workgroup owns what it owns in
+ * lmi_gemm_skinny_hl (two column blocks: hi rows | lo rows), above 32 weight rows (four blocks).  LMI_EINVAL: M < 1 or M > 32; a non-null
+ * row_bias_dev (there is no wide form of lmi_rope_qkv_skinny_hl_biased: shared-prefix decode keeps the 8-pair step). */
+int lmi_gemm_skinny_wide_hl(const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, int packed,
+                            const float* rowsq_in, int rowsq_parts, int norm_dim, float norm_eps, void* norm_out, int ld_norm, const float* norm_gamma,
+                            float* rowsq_out, int dtype, void* stream);
+int lmi_rope_qkv_skinny_wide_hl(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw,
+                                int ldx, int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all,
+                                const float* sin_all, void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev,
+                                const int* row_bias_dev, int dtype, void* stream);
+
 /* Batched decode behind a SHARED PREFIX (several questions about the same images: the prefix K / V exist once and every step reads them
  * once for the whole batch).  One query row per sequence, row s of q; sequence s attends to
  *     [k_prefix / v_prefix rows 0 .. *prefix_len) ; pooled rows k_begin[s] .. k_begin[s] + k_len[s]) of k / v],

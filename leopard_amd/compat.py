@@ -74,8 +74,10 @@ class LeopardForConditionalGeneration(DecodeBatchLimitOption):
     # ---- loading ---------------------------------------------------------------------------------------------
     @classmethod
     def from_pretrained(cls, path: str, torch_dtype=torch.float32, compute_dtype=torch.float16, ops: Optional[Ops] = None,
-                        precision: Optional[str] = None, tp_rank: int = 0, tp_size: int = 1, decode_batch_limit: Optional[int] = None):
-        """``precision``: see resolve_precision.  ``decode_batch_limit`` (also a settable attribute): the most sequences generate_stream /
+                        precision: Optional[str] = None, tp_rank: int = 0, tp_size: int = 1, decode_batch_limit: Optional[int] = None,
+                        decode_pair_limit: Optional[int] = None):
+        """``precision``: see resolve_precision.  ``decode_pair_limit`` (also a settable attribute): the most sequences a precision mode decodes on
+        the pair step (LeopardEngine.decode_pair_limit; 8 .. 32, default 8).  ``decode_batch_limit`` (also a settable attribute): the most sequences generate_stream /
         generate_batch decode in one step (LeopardEngine.decode_batch_limit; default 16).  ``tp_size`` > 1 (SURVEY.md 8 f1 "optional TP pre-sharding on load"): this process holds
         tensor-parallel shard ``tp_rank`` of the LLM — the checkpoint's tensors are sliced while they stream to the device
         (EngineWeights.build) — and needs an initialised process group of that size (leopard_amd.dist.init) by the time ``.to(device)`` runs."""
@@ -85,6 +87,8 @@ class LeopardForConditionalGeneration(DecodeBatchLimitOption):
         m.generation_defaults, m.beam_defaults = sampling.read_generation_defaults(path)
         if decode_batch_limit is not None:
             m.decode_batch_limit = decode_batch_limit
+        if decode_pair_limit is not None:
+            m.decode_pair_limit = decode_pair_limit
         return m
 
     def eval(self):

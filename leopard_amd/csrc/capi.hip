@@ -664,12 +664,13 @@ int skinny_impl(const void* W, const void* X, void* out, int M, int N, int K, in
 }
 
 // the wide form (csrc/skinny.h skinny_wide_kernel): two column blocks up to 32 rows, four above; 32 weight rows per workgroup at four
-template <typename T, int LAYOUT, int MB>
+// (HL, the pair form: M counts pairs, two blocks up to 16 pairs, four up to 32)
+template <typename T, int LAYOUT, int MB, bool HL = false>
 int skinny_wide_launch(const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, void* stream,
                        const RopeEpi& rp, const SkinnyNorm& nm) {
     const bool pair = epilogue == LMI_SKINNY_SWIGLU || epilogue == 4;
     const int units = pair ? N / 32 : (MB == 4 ? (N / 16 + 1) / 2 : N / 16);
-#define LMI_SK(E) LMI_LAUNCH((skinny_wide_kernel<T, E, LAYOUT, MB>), dim3(units), dim3(512), 0, stream, (const T*)W, (const T*)X, out, M, N, K, ldw, ldx, ldo, rp, nm)
+#define LMI_SK(E) LMI_LAUNCH((skinny_wide_kernel<T, E, LAYOUT, MB, HL>), dim3(units), dim3(512), 0, stream, (const T*)W, (const T*)X, out, M, N, K, ldw, ldx, ldo, rp, nm)
     switch (epilogue) {
         case LMI_SKINNY_STORE: LMI_SK(SK_STORE_T); break;
         case LMI_SKINNY_RESIDUAL: LMI_SK(SK_RESID_F32); break;
@@ -678,14 +679,17 @@ int skinny_wide_launch(const void* W, const void* X, void* out, int M, int N, in
         default: LMI_SK(SK_STORE_F32); break;
     }
 #undef LMI_SK
-    return check_launch("lmi_gemm_skinny_wide");
+    return check_launch(HL ? "lmi_gemm_skinny_wide_hl" : "lmi_gemm_skinny_wide");
 }
 
-// one dispatch for every skinny entry: wide = 0 -> skinny_gemm_kernel (M <= 16), wide = 1 -> skinny_wide_kernel (M <= 64)
+// one dispatch for every skinny entry: wide = 0 -> skinny_gemm_kernel (M <= 16), wide = 1 -> skinny_wide_kernel (M <= 64; with nm.hl its
+// pair form, M <= 32 pairs)
 template <typename T, int LAYOUT>
 int skinny_any(int wide, const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, void* stream,
                const RopeEpi& rp, const SkinnyNorm& nm) {
     if (!wide) return skinny_impl<T, LAYOUT>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, rp, nm);
+    if (nm.hl && M <= 16) return skinny_wide_launch<T, LAYOUT, 2, true>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, rp, nm);
+    if (nm.hl) return skinny_wide_launch<T, LAYOUT, 4, true>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, rp, nm);
     if (M <= 32) return skinny_wide_launch<T, LAYOUT, 2>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, rp, nm);
     return skinny_wide_launch<T, LAYOUT, 4>(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, stream, rp, nm);
 }
@@ -1605,7 +1609,8 @@ static int gemm_skinny_entry(const void* W, const void* X, void* out, int M, int
                              float* rowsq_out, int dtype, void* stream, int hl, int wide = 0) {
     const int max_m = wide ? 64 : 16;
     if (!W || !X || !out) return fail(LMI_EINVAL, "lmi_gemm_skinny: null pointer");
-    if (hl && 2 * M > 16) return fail(LMI_EINVAL, "lmi_gemm_skinny_hl: the hi + lo row pairs need 2 M <= 16 (M = %d)", M);
+    if (hl && wide && (M < 1 || M > 32)) return fail(LMI_EINVAL, "lmi_gemm_skinny_wide_hl: 1 <= M <= 32 hi + lo row pairs (M = %d)", M);
+    if (hl && !wide && 2 * M > 16) return fail(LMI_EINVAL, "lmi_gemm_skinny_hl: the hi + lo row pairs need 2 M <= 16 (M = %d)", M);
     if (M < 0 || M > max_m || N <= 0 || K <= 0 || (K % 128) || epilogue < LMI_SKINNY_STORE || epilogue > LMI_SKINNY_STORE_F32 ||
         (N % (epilogue == LMI_SKINNY_SWIGLU ? 64 : 16)))
         return fail(LMI_EINVAL, "lmi_gemm_skinny: need M <= %d, K %% 128 == 0, N %% 16 == 0 (SwiGLU: N %% 64 == 0) (M=%d N=%d K=%d)", max_m, M, N, K);
@@ -1673,12 +1678,21 @@ int lmi_gemm_skinny_wide(const void* W, const void* X, void* out, int M, int N, 
                              rowsq_out, dtype, stream, 0, 1);
 }
 
+int lmi_gemm_skinny_wide_hl(const void* W, const void* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, int epilogue, int packed,
+                            const float* rowsq_in, int rowsq_parts, int norm_dim, float norm_eps, void* norm_out, int ld_norm, const float* norm_gamma,
+                            float* rowsq_out, int dtype, void* stream) {
+    return gemm_skinny_entry(W, X, out, M, N, K, ldw, ldx, ldo, epilogue, packed, rowsq_in, rowsq_parts, norm_dim, norm_eps, norm_out, ld_norm, norm_gamma,
+                             rowsq_out, dtype, stream, 1, 1);
+}
+
 static int rope_qkv_skinny_entry(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,
                                  int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all, const float* sin_all,
                                  void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, int dtype, void* stream, int hl,
                                  const int* row_bias_dev = nullptr, int wide = 0) {
     const int max_m = wide ? 64 : 16;
-    if (hl && 2 * M > 16) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny_hl: the hi + lo row pairs need 2 M <= 16 (M = %d)", M);
+    if (hl && wide && (M < 1 || M > 32)) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny_wide_hl: 1 <= M <= 32 hi + lo row pairs (M = %d)", M);
+    if (wide && row_bias_dev) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny_wide_hl: a row_bias has no wide form");
+    if (hl && !wide && 2 * M > 16) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny_hl: the hi + lo row pairs need 2 M <= 16 (M = %d)", M);
     if (!Wqkv_rope || !X || !qkv || !cos_all || !sin_all || !k_cache || !v_cache || !pos_rows_dev) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny: null pointer");
     if (head_dim != 128) return fail(LMI_EINVAL, "lmi_rope_qkv_skinny: head_dim %d (only 128)", head_dim);
     const int N = (n_q_heads + 2 * n_kv_heads) * head_dim;
@@ -1714,6 +1728,14 @@ int lmi_rope_qkv_skinny_wide(const void* Wqkv_rope, const void* X, void* qkv, in
                              void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev, int dtype, void* stream) {
     return rope_qkv_skinny_entry(Wqkv_rope, X, qkv, M, n_q_heads, n_kv_heads, head_dim, K, ldw, ldx, ldo, packed, rowsq_in, rowsq_parts, norm_eps, cos_all,
                                  sin_all, k_cache, v_cache, ld_cache, cache_stride, pos_rows_dev, dtype, stream, 0, nullptr, 1);
+}
+
+int lmi_rope_qkv_skinny_wide_hl(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw,
+                                int ldx, int ldo, int packed, const float* rowsq_in, int rowsq_parts, float norm_eps, const float* cos_all,
+                                const float* sin_all, void* k_cache, void* v_cache, int ld_cache, int64_t cache_stride, const int* pos_rows_dev,
+                                const int* row_bias_dev, int dtype, void* stream) {
+    return rope_qkv_skinny_entry(Wqkv_rope, X, qkv, M, n_q_heads, n_kv_heads, head_dim, K, ldw, ldx, ldo, packed, rowsq_in, rowsq_parts, norm_eps, cos_all,
+                                 sin_all, k_cache, v_cache, ld_cache, cache_stride, pos_rows_dev, dtype, stream, 1, row_bias_dev, 1);
 }
 
 int lmi_rope_qkv_skinny_hl(const void* Wqkv_rope, const void* X, void* qkv, int M, int n_q_heads, int n_kv_heads, int head_dim, int K, int ldw, int ldx,

@@ -227,8 +227,8 @@ __global__ void __launch_bounds__(512) skinny_gemm_kernel(const T* W, const T* X
 }
 
 // ------------------------------------------------------------------------------------------------
-// The wide form: M <= 16 MB batch rows (MB = 2 or 4 column blocks of the 16x16x32 MFMA), every epilogue of skinny_gemm_kernel but the hl
-// pairs.  Row m gets the BITS skinny_gemm_kernel gives it in any launch of at most 16 rows that holds it: an MFMA output column depends on
+// The wide form: M <= 16 MB batch rows (MB = 2 or 4 column blocks of the 16x16x32 MFMA), every epilogue of skinny_gemm_kernel (the hl
+// pairs: HL, below).  Row m gets the BITS skinny_gemm_kernel gives it in any launch of at most 16 rows that holds it: an MFMA output column depends on
 // its own X row only, and everything that orders a row's sums is kept — 128-element k-steps, step s on wave s % 8, chunks c = 0..3 within a
 // step, the w = 0..7 sum of the partial tiles, the 32-lane rstd reduction of the consumer, the n = 0..15 column sum of the producer.
 // What differs is what a workgroup owns and how X is held:
@@ -243,8 +243,17 @@ __global__ void __launch_bounds__(512) skinny_gemm_kernel(const T* W, const T* X
 //     106 - 114, 137 - 148 and 200 - 204, no scratch.  Holding the MB = 2 pairs to 128 (two workgroups per CU, as the one-block forms have)
 //     makes them spill 12 - 18 registers, so they run one workgroup per CU like MB = 4.
 //   * the 8 partial tiles of ONE column block meet in LDS at a time (16 KiB as before), column block after column block.
+// HL = true, the pair form (lmi_gemm_skinny_wide_hl / lmi_rope_qkv_skinny_wide_hl): M <= 8 MB PAIRS in the buffer layout of skinny_gemm_kernel's
+// hl mode (X rows [0, M) = T(x), rows [M, 2 M) = T(x - T(x)); 16-bit operand outputs as rows m and m + M again), pair m with the bits that
+// kernel gives it in any launch of at most 8 pairs that holds it.  There the lo row is column m + M of the SAME MFMA block as its hi row; here
+// the X rows are addressed by pair, not by contiguity: column blocks [0, MB / 2) load the hi rows 16 pb + i, blocks [MB / 2, MB) their lo
+// partners M + 16 pb + i, so lane (i, g) of block pb and of block pb + MB / 2 hold the two halves of one pair whatever M is.  The epilogue takes
+// the blocks two at a time — the hi and the lo partials of pair block pb in LDS together (32 KiB) — and adds them as that kernel does: the
+// w = 0..7 sum of the hi partials, the w = 0..7 sum of the lo partials, hi + lo, then rstd, the epilogue arithmetic and y - (float)hi.  The main
+// loop is that of the plain form at the same MB; compiled registers per lane: 105 - 112 (MB 2, one block), 136 - 150 (MB 2, pair) and 196 - 202
+// (MB 4), no scratch, the occupancy of the plain form (4 / 3 / 2 waves per SIMD); LDS 16 - 17 KiB (one block) and 32 - 34 KiB.
 // ------------------------------------------------------------------------------------------------
-template <typename T, int EPI, int LAYOUT, int MB>
+template <typename T, int EPI, int LAYOUT, int MB, bool HL = false>
 __global__ void __launch_bounds__(512) skinny_wide_kernel(const T* W, const T* X, void* out, int M, int N, int K, int ldw, int ldx, int ldo, RopeEpi rp,
                                                           SkinnyNorm nm) {
     typedef typename vec_of<T>::x8 T8;
@@ -253,15 +262,17 @@ __global__ void __launch_bounds__(512) skinny_wide_kernel(const T* W, const T* X
     constexpr int NW = (PAIR || MB == 4) ? 2 : 1;                  // weight row blocks per workgroup
     constexpr int BROWS = PAIR ? 32 : 16;                          // rows from block 0 to block 1: the pair partner / the next block
     constexpr int DEPTH = NW == 2 ? 2 : 3;                         // k-steps of WEIGHT loads in flight per wave
-    __shared__ float part[8][NW][64][4];
-    __shared__ float rstd_s[16 * MB], sq_s[NW][16][17];
+    constexpr int PB = HL ? MB / 2 : MB;                           // column blocks of output rows (HL: pair blocks, each a hi and a lo column block)
+    constexpr int LO = HL ? 1 : 0;                                 // part[LO]: the lo partials of a pair block (plain form: none)
+    __shared__ float part[1 + LO][8][NW][64][4];
+    __shared__ float rstd_s[16 * PB], sq_s[NW][16][17];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
     const int i = lane & 15, g = lane >> 4;
     const int unit = blockIdx.x;
     // consumer: as skinny_gemm_kernel, once per column block (row 16 mb + (tid >> 5))
-    float ssq[MB];
+    float ssq[PB];
 #pragma unroll
-    for (int mb = 0; mb < MB; ++mb) {
+    for (int mb = 0; mb < PB; ++mb) {
         ssq[mb] = 0.f;
         const int m = 16 * mb + (tid >> 5);
         if (nm.rowsq_in && m < M)
@@ -294,7 +305,9 @@ __global__ void __launch_bounds__(512) skinny_wide_kernel(const T* W, const T* X
         const int k0 = (wave + 8 * s) * 128 + 32 * c;
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb) {
-            if (i + 16 * mb < M) xv[c][mb] = *(const T8*)(xrow + (long)(16 * mb) * ldx + k0);
+            // HL: block mb holds the hi (mb < PB) or the lo (row + M) half of pair block mb % PB
+            const int m0 = 16 * (mb % PB), r0 = (HL && mb >= PB) ? m0 + M : m0;
+            if (i + m0 < M) xv[c][mb] = *(const T8*)(xrow + (long)r0 * ldx + k0);
             else {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) xv[c][mb][e] = (T)0.0f;
@@ -340,7 +353,7 @@ __global__ void __launch_bounds__(512) skinny_wide_kernel(const T* W, const T* X
     }
     if (nm.rowsq_in) {
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb) {
+        for (int mb = 0; mb < PB; ++mb) {
             float q = ssq[mb];
 #pragma unroll
             for (int msk = 16; msk >= 1; msk >>= 1) q += shfl_xor(q, msk);
@@ -349,10 +362,13 @@ __global__ void __launch_bounds__(512) skinny_wide_kernel(const T* W, const T* X
     }
     const bool producer = EPI == SK_RESID_F32 && nm.norm_out;
 #pragma unroll
-    for (int mb = 0; mb < MB; ++mb) {
+    for (int mb = 0; mb < PB; ++mb) {
         if (16 * mb < M) {                                          // uniform: a column block without a live row has nothing to finish
 #pragma unroll
-            for (int b = 0; b < NW; ++b) *(f32x4*)part[wave][b][lane] = acc[b][mb];
+            for (int b = 0; b < NW; ++b) {
+                *(f32x4*)part[0][wave][b][lane] = acc[b][mb];
+                if (HL) *(f32x4*)part[LO][wave][b][lane] = acc[b][(mb + PB) % MB];
+            }
             __syncthreads();
             if (tid < 256) {
                 const int l = tid & 63, r = tid >> 6;
@@ -360,9 +376,15 @@ __global__ void __launch_bounds__(512) skinny_wide_kernel(const T* W, const T* X
                 float v[NW];
 #pragma unroll
                 for (int b = 0; b < NW; ++b) {
-                    float s = part[0][b][l][r];
+                    float s = part[0][0][b][l][r];
 #pragma unroll
-                    for (int w = 1; w < 8; ++w) s += part[w][b][l][r];
+                    for (int w = 1; w < 8; ++w) s += part[0][w][b][l][r];
+                    if (HL && m < M) {                              // + the lo row's product: hi sum, lo sum, then their sum (as skinny_gemm_kernel)
+                        float s2 = part[LO][0][b][l][r];
+#pragma unroll
+                        for (int w = 1; w < 8; ++w) s2 += part[LO][w][b][l][r];
+                        s += s2;
+                    }
                     v[b] = nm.rowsq_in ? s * rstd_s[m] : s;
                 }
                 if (m < M) {
@@ -395,21 +417,28 @@ __global__ void __launch_bounds__(512) skinny_wide_kernel(const T* W, const T* X
                     } else if (EPI == SK_SWIGLU_T) {
                         const float gt = v[0], up = v[NW - 1];
                         const float y = sep_rn(gt / (1.0f + fexp(-gt)) * up);
-                        ((T*)out)[(long)m * ldo + (unit >> 1) * 32 + (unit & 1) * 16 + n] = (T)y;
+                        const T hi = (T)y;
+                        ((T*)out)[(long)m * ldo + (unit >> 1) * 32 + (unit & 1) * 16 + n] = hi;
+                        if (HL) ((T*)out)[(long)(m + M) * ldo + (unit >> 1) * 32 + (unit & 1) * 16 + n] = (T)(y - (float)hi);
                     } else {
 #pragma unroll
                         for (int b = 0; b < NW; ++b) {
                             if (b < live) {
                                 const int col = row0 + 16 * b + n;
-                                if (EPI == SK_STORE_T) ((T*)out)[(long)m * ldo + col] = (T)v[b];
-                                else if (EPI == SK_STORE_F32) ((float*)out)[(long)m * ldo + col] = v[b];
+                                if (EPI == SK_STORE_T) {
+                                    const T hi = (T)v[b];
+                                    ((T*)out)[(long)m * ldo + col] = hi;
+                                    if (HL) ((T*)out)[(long)(m + M) * ldo + col] = (T)(v[b] - (float)hi);
+                                } else if (EPI == SK_STORE_F32) ((float*)out)[(long)m * ldo + col] = v[b];
                                 else {
                                     float* xo = (float*)out + (long)m * ldo + col;
                                     const float xn = *xo + v[b];
                                     *xo = xn;
                                     if (nm.norm_out) {
                                         const float y = sep_rn(xn * nm.gamma[col]);
-                                        ((T*)nm.norm_out)[(long)m * nm.ld_norm + col] = (T)y;
+                                        const T hi = (T)y;
+                                        ((T*)nm.norm_out)[(long)m * nm.ld_norm + col] = hi;
+                                        if (HL) ((T*)nm.norm_out)[(long)(m + M) * nm.ld_norm + col] = (T)(y - (float)hi);
                                         sq_s[b][n][l & 15] = xn * xn;
                                     }
                                 }

@@ -429,6 +429,7 @@ class LeopardEngine:
         self._stream_cache = None      # the KV cache generate_stream prefills a newcomer into before its rows move to a slot
         self._batch_states: Dict[int, DecodeState] = {}   # B -> state of the batched decode step (_batch_state)
         self._decode_batch_limit = self.MAX_DECODE_BATCH   # decode_batch_limit: sequences per captured step of generate_stream / generate_batch
+        self._decode_pair_limit = self.PAIR_DECODE_BATCH   # decode_pair_limit: the most sequences a precision mode decodes on the pair (hl) step
         self._skinny_pack = None       # second copy of the LLM weights in the skinny-M operand order (_skinny_weights)
         self._head_pack = None         # lm_head in the packed order (_skinny_head)
         # ONE copy of the LLM weights (default; LMI_PACK_LLM_WEIGHTS=0 / pack_llm_weights=False keep the nn.Linear layout): see pack_llm_weights
@@ -480,13 +481,16 @@ class LeopardEngine:
         if self.lo4 and self.device.type == "cuda":
             self._lo4_weights("llm")                          # the multi-GB quantisation happens HERE, not inside the first (timed) prefill
 
-    def decode_hl(self, B: int = 1) -> bool:
+    def decode_hl(self, B: int = 1, pair_limit: Optional[int] = None) -> bool:
         """Decode precision mode (round 6): with ``precision`` = "lo4" / "split" the captured decode step hands every projection operand over as a
         pair of 16-bit rows — T(x) and T(x - T(x)) — through the M <= 16 kernels (lmi_gemm_skinny_hl ...): the hand-over roundings of the token's
         own path through the layers, which are what its logits' error is made of, are gone, at no extra weight traffic.  Needs the packed one-copy
-        weight layout (the default on one rank), the folded norms and 2 B <= 16; otherwise the step is the fast one."""
+        weight layout (the default on one rank), the folded norms and B <= decode_pair_limit (8 pairs are the 16 rows of those kernels; above, the
+        step runs on lmi_gemm_skinny_wide_hl ...: M <= 32 pairs); otherwise the step is the fast one.  ``pair_limit``: a caller's own cap
+        (generate_shared keeps the 8-pair step)."""
         D = self.cfg.text_config.hidden_size
-        return bool((self.lo4 or self.split_operands) and self.decode_precision and self.tp_size == 1 and self.llm_packed and 2 * B <= 16
+        limit = self._decode_pair_limit if pair_limit is None else min(self._decode_pair_limit, pair_limit)
+        return bool((self.lo4 or self.split_operands) and self.decode_precision and self.tp_size == 1 and self.llm_packed and B <= limit
                     and self.skinny_fold_norm and D % 16 == 0 and self.cfg.text_config.head_dim == 128
                     and all(L.qkv_w_rope is not None for L in self.W.llm_layers))
 
@@ -1710,12 +1714,12 @@ class LeopardEngine:
     # HIP graph over static buffers; the token id and the position live in device memory (lmi_rope_qk_at, device
     # cu_seqlens), the graph itself takes the argmax and advances the position, and the host only reads the new token.
     # ------------------------------------------------------------------------------------------------
-    def _decode_buffers(self, B: int, capacity: int, prefix_capacity: int = 0) -> DecodeState:
+    def _decode_buffers(self, B: int, capacity: int, prefix_capacity: int = 0, pair_limit: Optional[int] = None) -> DecodeState:
         """What the batch-1 and the pooled decode state allocate alike: a function of (B, capacity) under the engine's current mode
         (``prefix_capacity`` > 0: the shared-prefix step — positions run to prefix_capacity + capacity, the workspace is that launch's)."""
         W, tc, dev = self.W, self.cfg.text_config, self.device
         (H, KV), hd, D = self._llm_heads(), tc.head_dim, tc.hidden_size
-        hl = self.decode_hl(B)
+        hl = self.decode_hl(B, pair_limit)
         R = 2 * B if hl else B
         cos, sin = self.rope_tables(torch.arange(prefix_capacity + capacity))
         ws_elems = (self.ops.decode_shared_workspace_elems(B, H, hd, prefix_capacity, capacity) if prefix_capacity
@@ -2157,14 +2161,16 @@ class LeopardEngine:
     HIST = 8                           # continuous batching: decode steps between two host looks at the produced tokens
     MAX_EOS = 4                        # eos ids held on the device
     WIDE_DECODE_BATCH = 64             # rows of one lmi_gemm_skinny_wide launch (four column blocks): the most decode_batch_limit admits
+    PAIR_DECODE_BATCH = 8              # hi + lo pairs of one lmi_gemm_skinny_hl launch (2 M <= 16 rows): the default decode_pair_limit
+    WIDE_PAIR_DECODE_BATCH = 32        # pairs of one lmi_gemm_skinny_wide_hl launch (four column blocks): the most decode_pair_limit admits
 
     @property
     def decode_batch_limit(self) -> int:
         """The most sequences generate_stream / generate_batch decode in ONE captured step (default MAX_DECODE_BATCH).  Above 16 the step's
         projections and head run on the wide kernels (lmi_gemm_skinny_wide, lmi_rope_qkv_skinny_wide: M <= 64), which give every row the
         bits the 16-row kernels give it, so a request decodes to the same tokens at any width; a precision mode ("lo4" / "split") decodes
-        more than 8 sequences on the fast step, as it does 9 .. 16.  The pooled KV cache is B x capacity rows per layer, and the pools of the
-        two most recent batch sizes are kept: size the limit to the memory left beside the weights."""
+        more than decode_pair_limit sequences (default 8) on the fast step, as it does 9 .. 16.  The pooled KV cache is B x capacity rows per
+        layer, and the pools of the two most recent batch sizes are kept: size the limit to the memory left beside the weights."""
         return self._decode_batch_limit
 
     @decode_batch_limit.setter
@@ -2173,6 +2179,23 @@ class LeopardEngine:
             raise ValueError(f"decode_batch_limit must be an integer in 1 .. {self.WIDE_DECODE_BATCH}, got {value!r}")
         self._decode_batch_limit = value
 
+    @property
+    def decode_pair_limit(self) -> int:
+        """The most sequences a precision mode ("lo4" / "split") decodes on the pair step (decode_hl) in generate_stream / generate_batch: 8 ..
+        32, default 8 — the pairs of the 16-row kernels, with which every call launches and replays what it always did.  Above 8 sequences the
+        step's projections and head run on lmi_gemm_skinny_wide_hl / lmi_rope_qkv_skinny_wide_hl (M <= 32 pairs), which give every pair the bits
+        the 8-pair entries give it: a request decodes to the same tokens and log-probs at any width up to the limit.  More sequences than the
+        limit (and 33 .. 64 always: 64 pairs would be 128 batch rows) decode on the fast step.  generate_shared and generate_beams keep the
+        8-pair step.  Setting another value drops the pooled decode states: a step captured under one limit is never replayed under another."""
+        return self._decode_pair_limit
+
+    @decode_pair_limit.setter
+    def decode_pair_limit(self, value) -> None:
+        _check_pair_limit(value)
+        if value != self._decode_pair_limit:
+            self._batch_states = {}
+        self._decode_pair_limit = value
+
     def _batch_decode_supported(self) -> bool:
         """lmi_gemm_skinny needs K % 128 == 0 and N % 16 == 0 (gate/up: % 64); the pooled decode attention head_dim 128."""
         W, tc = self.W, self.cfg.text_config
@@ -2180,13 +2203,13 @@ class LeopardEngine:
         return (hd == 128 and D % 128 == 0 and W.llm_ff % 128 == 0 and (2 * W.llm_ff) % 64 == 0 and ((H + 2 * KV) * hd) % 16 == 0 and
                 W.lm_head.shape[0] % 16 == 0 and D % 16 == 0)
 
-    def _pooled_state(self, key, fits, build) -> DecodeState:
-        """The pooled decode state kept under ``key``: reused when it ``fits`` and belongs to the current precision mode, else built anew
-        (``build``).  Bounded: a serving process that sees many batch sizes keeps the pools of the two most recent ones (each is B x capacity
-        KV rows)."""
+    def _pooled_state(self, key, fits, build, hl: bool) -> DecodeState:
+        """The pooled decode state kept under ``key``: reused when it ``fits``, belongs to the current precision mode and is the pair (``hl``) or
+        the fast step as the caller gets it now (decode_pair_limit, a caller's own cap), else built anew (``build``).  Bounded: a serving
+        process that sees many batch sizes keeps the pools of the two most recent ones (each is B x capacity KV rows)."""
         states = self._batch_states
         st = states.get(key)
-        if st is not None and fits(st) and st.mode == (self.precision, self.decode_precision):
+        if st is not None and fits(st) and st.mode == (self.precision, self.decode_precision) and st.hl == hl:
             return st
         st = build()
         while len(states) >= 2:
@@ -2194,14 +2217,14 @@ class LeopardEngine:
         states[key] = st
         return st
 
-    def _batch_state(self, B: int, need: int) -> DecodeState:
+    def _batch_state(self, B: int, need: int, pair_limit: Optional[int] = None) -> DecodeState:
         """Static buffers + pooled KV cache + captured graph of a B-sequence decode step (kept per engine and reused: the graph reads
         positions / key counts from device memory and its launch geometry depends on (B, capacity) only)."""
         def build():
-            st = self._decode_buffers(B, (need + 1023) // 1024 * 1024)
+            st = self._decode_buffers(B, (need + 1023) // 1024 * 1024, pair_limit=pair_limit)
             self._pool_buffers(st)
             return st
-        return self._pooled_state(B, lambda st: st.capacity >= need, build)
+        return self._pooled_state(B, lambda st: st.capacity >= need, build, self.decode_hl(B, pair_limit))
 
     SHARED_OWN_ROWS = 256              # shared-prefix decode: a slot's own rows (question + new tokens) are rounded up to this ...
     SHARED_PREFIX_ROWS = 1024          # ... and the one prefix copy to this, so that calls of about the same shape reuse one captured step
@@ -2232,7 +2255,7 @@ class LeopardEngine:
             own = (need_own + self.SHARED_OWN_ROWS - 1) // self.SHARED_OWN_ROWS * self.SHARED_OWN_ROWS
             pcap = (need_prefix + self.SHARED_PREFIX_ROWS - 1) // self.SHARED_PREFIX_ROWS * self.SHARED_PREFIX_ROWS
             self._batch_states.pop(("shared", B), None)                # the pool it replaces goes first: never two of one batch size
-            st = self._decode_buffers(B, own, prefix_capacity=pcap)
+            st = self._decode_buffers(B, own, prefix_capacity=pcap, pair_limit=self.PAIR_DECODE_BATCH)
             self._pool_buffers(st)
             n_layers = len(self.W.llm_layers)
             st.kp = [torch.zeros(pcap, KV * hd, dtype=self.dtype, device=dev) for _ in range(n_layers)]
@@ -2240,7 +2263,8 @@ class LeopardEngine:
             st.prefix_capacity = pcap
             st.prefix_len = torch.ones(1, dtype=torch.int32, device=dev)
             return st
-        return self._pooled_state(("shared", B), lambda st: st.capacity >= need_own and st.prefix_capacity >= need_prefix, build)
+        return self._pooled_state(("shared", B), lambda st: st.capacity >= need_own and st.prefix_capacity >= need_prefix, build,
+                                  self.decode_hl(B, self.PAIR_DECODE_BATCH))
 
     def _pool_buffers(self, st: DecodeState) -> None:
         """The pooled KV slots and the device side of continuous batching of a B-sequence decode state."""
@@ -2291,11 +2315,12 @@ class LeopardEngine:
         fold = self.skinny_fold_norm and D % 16 == 0 and all(L.qkv_w_rope is not None for L in W.llm_layers) and hd == 128
         hl = st.hl                                                    # decode precision mode: operands are [hi rows; lo rows] pairs (decode_hl)
         assert not hl or fold
-        # a wide step (decode_batch_limit > 16): launch for launch the same step on the M <= 64 entries, which give every row the bits of the
-        # 16-row kernels and have no pair and no row_bias form (decode_hl and the shared-prefix step keep their own limits)
-        wide = st.B > self.MAX_DECODE_BATCH
-        assert not wide or (not hl and st.prefix_len is None)
-        gemm, hlk = (ops.gemm_skinny_wide, {}) if wide else (ops.gemm_skinny, {"hl": hl})
+        # a wide step (decode_batch_limit > 16; a pair step of more than 8, decode_pair_limit): launch for launch the same step on the
+        # M <= 64 entries (pairs: M <= 32), which give every row the bits of the 16-row kernels and have no row_bias form (the shared-prefix step
+        # keeps its own limits)
+        wide = st.B > (self.PAIR_DECODE_BATCH if hl else self.MAX_DECODE_BATCH)
+        assert not wide or st.prefix_len is None
+        gemm, hlk = ((ops.gemm_skinny_wide_hl if hl else ops.gemm_skinny_wide), {}) if wide else (ops.gemm_skinny, {"hl": hl})
         norm = self._rmsnorm_rows32 if wide else ops.rmsnorm
         for i, L in enumerate(W.llm_layers):
             rope_fused = L.qkv_w_rope is not None and hd == 128
@@ -2307,8 +2332,9 @@ class LeopardEngine:
             elif not fold or i == 0:
                 norm(st.x, L.in_norm, st.h, eps)
             if rope_fused and wide:
-                ops.rope_qkv_skinny_wide(qkv_w, st.h, st.qkv, H, KV, hd, st.cos, st.sin, k_list[i], v_list[i], capacity, st.pos, packed,
-                                         rowsq_in=st.sq_b if fold and i > 0 else None, norm_eps=eps)
+                rope_wide = ops.rope_qkv_skinny_wide_hl if hl else ops.rope_qkv_skinny_wide
+                rope_wide(qkv_w, st.h, st.qkv, H, KV, hd, st.cos, st.sin, k_list[i], v_list[i], capacity, st.pos, packed,
+                          rowsq_in=st.sq_b if fold and i > 0 else None, norm_eps=eps)
             elif rope_fused:
                 ops.rope_qkv_skinny(qkv_w, st.h, st.qkv, H, KV, hd, st.cos, st.sin, k_list[i], v_list[i], capacity, st.pos, packed,
                                     rowsq_in=st.sq_b if fold and i > 0 else None, norm_eps=eps, hl=hl, row_bias=st.prefix_len)
@@ -2364,7 +2390,11 @@ class LeopardEngine:
         if st.hl:                                                     # decode precision mode: the head's operand as a pair too (the batch-1 step's head reads the fp32 row)
             ops.rmsnorm(st.x, W.final_norm, st.hf32, eps)
             ops.split_rows_hl(st.hf32, st.h)
-            ops.gemm_skinny(self._skinny_head() if self.skinny_packed else W.lm_head, st.h, st.logits, 3, hl=True)
+            head = self._skinny_head() if self.skinny_packed else W.lm_head
+            if st.B > self.PAIR_DECODE_BATCH:                         # a wide pair step (decode_pair_limit): the head on the M <= 32 pair entry
+                ops.gemm_skinny_wide_hl(head, st.h, st.logits, 3)
+            else:
+                ops.gemm_skinny(head, st.h, st.logits, 3, hl=True)
         elif st.B > self.MAX_DECODE_BATCH:                            # a wide step: the final norm in chunks, the head on the M <= 64 entry
             self._rmsnorm_rows32(st.x, W.final_norm, st.h, eps)
             ops.gemm_skinny_wide(self._skinny_head() if self.skinny_packed else W.lm_head, st.h, st.logits, 3)
@@ -2975,7 +3005,7 @@ class LeopardEngine:
                     self._load_rows([(prefix, 0, P)], st.kp, st.vp, 0)   # the one prefix copy (the captured step reads state-owned memory only)
                     st.prefix_len.fill_(P)
                 else:
-                    st = self._batch_state(len(chunk), P + max(lens) + max_new_tokens)
+                    st = self._batch_state(len(chunk), P + max(lens) + max_new_tokens, pair_limit=self.PAIR_DECODE_BATCH)
                 for j in range(len(chunk)):
                     self._load_rows(own[j] if decode == "shared" else whole[j], st.k, st.v, j * st.capacity)
                 toks += self._greedy_loop_batch(st, prompts, first, [P + s for s in lens], max_new_tokens, eos, None if sampling is None else req,
@@ -3149,7 +3179,31 @@ class DecodeBatchLimitOption:
         if getattr(self, "_engine", None) is not None:
             self._engine.decode_batch_limit = value
 
+    _decode_pair_limit: Optional[int] = None                        # ``decode_pair_limit`` (LeopardEngine.decode_pair_limit), kept the same way
+
+    @property
+    def decode_pair_limit(self) -> int:
+        eng = getattr(self, "_engine", None)
+        if eng is not None:
+            return eng.decode_pair_limit
+        return LeopardEngine.PAIR_DECODE_BATCH if self._decode_pair_limit is None else self._decode_pair_limit
+
+    @decode_pair_limit.setter
+    def decode_pair_limit(self, value) -> None:
+        _check_pair_limit(value)
+        self._decode_pair_limit = value
+        if getattr(self, "_engine", None) is not None:
+            self._engine.decode_pair_limit = value
+
     def _apply_decode_batch_limit(self) -> None:
         """Called by ``.to`` once the engine exists."""
         if self._decode_batch_limit is not None:
             self._engine.decode_batch_limit = self._decode_batch_limit
+        if self._decode_pair_limit is not None:
+            self._engine.decode_pair_limit = self._decode_pair_limit
+
+
+def _check_pair_limit(value) -> None:
+    lo, hi = LeopardEngine.PAIR_DECODE_BATCH, LeopardEngine.WIDE_PAIR_DECODE_BATCH
+    if isinstance(value, bool) or not isinstance(value, int) or not lo <= value <= hi:
+        raise ValueError(f"decode_pair_limit must be an integer in {lo} .. {hi}, got {value!r}")

@@ -167,8 +167,10 @@ class Idefics2ForConditionalGeneration(DecodeBatchLimitOption):
 
     @classmethod
     def from_pretrained(cls, path: str, torch_dtype=torch.float16, ops: Optional[Ops] = None, patch_validity: str = "any",
-                        precision: Optional[str] = None, decode_batch_limit: Optional[int] = None, **unused):
-        """``precision`` / ``LEOPARD_AMD_PRECISION``: see leopard_amd.compat.resolve_precision.  ``decode_batch_limit`` (also a settable
+                        precision: Optional[str] = None, decode_batch_limit: Optional[int] = None, decode_pair_limit: Optional[int] = None,
+                        **unused):
+        """``precision`` / ``LEOPARD_AMD_PRECISION``: see leopard_amd.compat.resolve_precision.  ``decode_pair_limit`` (also a settable
+        attribute): the most sequences a precision mode decodes on the pair step (LeopardEngine.decode_pair_limit; 8 .. 32, default 8).  ``decode_batch_limit`` (also a settable
         attribute): the most sequences generate_stream / generate_batch decode in one step (LeopardEngine.decode_batch_limit; default 16).  The reference loads this model in fp16
         (idefics2_multiimg.py:27-28), so the default for its request is the fast fp16 schedule; a float32 request selects lo4."""
         cfg = load_idefics2_config(path)
@@ -189,6 +191,8 @@ class Idefics2ForConditionalGeneration(DecodeBatchLimitOption):
         m.precision = resolve_precision(torch_dtype, dtype, precision)
         if decode_batch_limit is not None:
             m.decode_batch_limit = decode_batch_limit
+        if decode_pair_limit is not None:
+            m.decode_pair_limit = decode_pair_limit
         return m
 
     def eval(self):

@@ -400,6 +400,34 @@ class Ops:
             _ptr(k_cache), _ptr(v_cache), k_cache.stride(0), int(cache_stride), _ptr(pos_rows), _DT[w_rope.dtype], self._stream(qkv)))
         return qkv
 
+    def gemm_skinny_wide_hl(self, w, x, out, epilogue=0, packed=None, rowsq_in=None, norm_dim=0, norm_eps=0.0, norm_out=None, norm_gamma=None,
+                            rowsq_out=None):
+        """lmi_gemm_skinny_wide_hl: ``gemm_skinny(hl=True)`` for 1 .. 32 pairs (x holds 2 M rows [T(x); T(x - T(x))], 16-bit operand outputs are
+        pairs again); pair m has the bits ``gemm_skinny(hl=True)`` gives it in any launch of at most 8 pairs that holds it."""
+        N, K = w.shape
+        M = x.shape[0] // 2
+        if packed is None:
+            packed = getattr(w, "_lmi_packed", False)
+        assert x.shape[0] == 2 * M and (epilogue in (1, 3) or out.shape[0] == 2 * M) and (norm_out is None or norm_out.shape[0] == 2 * M)
+        self._check(self.lib.lmi_gemm_skinny_wide_hl(_ptr(w), _ptr(x), _ptr(out), M, N, K, w.stride(0), x.stride(0), out.stride(0), int(epilogue),
+                                                     int(bool(packed)), _ptr(rowsq_in), 0 if rowsq_in is None else rowsq_in.shape[1], int(norm_dim),
+                                                     float(norm_eps), _ptr(norm_out), 0 if norm_out is None else norm_out.stride(0), _ptr(norm_gamma),
+                                                     _ptr(rowsq_out), _DT[w.dtype], self._stream(out)))
+        return out
+
+    def rope_qkv_skinny_wide_hl(self, w_rope, x, qkv, n_q_heads, n_kv_heads, head_dim, cos_all, sin_all, k_cache, v_cache, cache_stride, pos_rows,
+                                packed=None, rowsq_in=None, norm_eps=0.0, row_bias=None):
+        """lmi_rope_qkv_skinny_wide_hl: ``rope_qkv_skinny(hl=True)`` for 1 .. 32 pairs (x holds 2 M rows, qkv M), pair for pair the same bits.
+        ``row_bias`` is refused by the entry: there is no wide form of the shared-prefix append."""
+        if packed is None:
+            packed = getattr(w_rope, "_lmi_packed", False)
+        self._check(self.lib.lmi_rope_qkv_skinny_wide_hl(
+            _ptr(w_rope), _ptr(x), _ptr(qkv), x.shape[0] // 2, n_q_heads, n_kv_heads, head_dim, w_rope.shape[1], w_rope.stride(0), x.stride(0),
+            qkv.stride(0), int(bool(packed)), _ptr(rowsq_in), 0 if rowsq_in is None else rowsq_in.shape[1], float(norm_eps), _ptr(cos_all), _ptr(sin_all),
+            _ptr(k_cache), _ptr(v_cache), k_cache.stride(0), int(cache_stride), _ptr(pos_rows), _ptr(None if row_bias is None else _bias_arg(row_bias)),
+            _DT[w_rope.dtype], self._stream(qkv)))
+        return qkv
+
     def llm_prefill_workspace(self, rows, hidden, n_q_heads, n_kv_heads, head_dim, ff, dtype):
         """lmi_llm_prefill_workspace_bytes -> (total bytes, [byte offset of LMI_WS_LLM_* buffer])."""
         import ctypes as C
