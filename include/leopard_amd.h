@@ -392,6 +392,25 @@ int lmi_decode_sample(const float* logits, int B, int vocab, int ld_logits, cons
                       const int* top_k, const float* top_p, const uint64_t* seed, int* step, int64_t* tok, int* pos, int* k_len, int* live,
                       int* budget, const int64_t* eos, int n_eos, int64_t* hist, int* hist_pos, int hist_len, void* stream);
 
+/* lmi_decode_sample with the rest of HF's warper chain after top-p, in HF's order: min_p, typical_p, epsilon_cutoff, eta_cutoff — per-row
+ * device arrays of length B, each nullable (null = off for every row).  With d_i = s_i - max s, w_i = expf(d_i) and S0 the kept prefix of
+ * lmi_decode_sample, each warper sees what the earlier ones left and renormalises over it:
+ *   min_p[b] = m in (0, 1] (0 = off):          keeps w_i >= m (relative to the top token, which always stays);
+ *   typical_p[b] = t in (0, 1) (>= 1 = off):   a_i = -log p_i, H = sum p_i a_i, sh_i = |a_i - H|; keeps sh_i <= c, c the sh of the first
+ *                                              token, sh ascending, at which the cumulative mass reaches ceil(t * mass) — whole tie groups at
+ *                                              c, a band of scores: the top token can be removed, as in HF;
+ *   epsilon_cutoff[b] = e in (0, 1) (0 = off): keeps p_i >= e and the tokens with the largest remaining score;
+ *   eta_cutoff[b] = h in (0, 1) (0 = off):     keeps p_i >= min(h, sqrt(h) * exp(-H)) and the tokens with the largest remaining score.
+ * Masses and entropies are sums of 2^-32 fixed-point terms, so the kept set does not depend on thread order, slot or B; the draw is
+ * lmi_decode_sample's Gumbel-max over the final set at the same Philox counter — with all four off, the same token.  The values live in
+ * device memory (new values never need a new graph capture), so a launch cannot read them: a value outside its range acts as off (min_p
+ * above 1 as 1) and never faults; LMI_EINVAL is for the host arguments, as lmi_decode_sample.  Callers check the ranges on the host
+ * (SamplingParams).  Exact rules: leopard_amd/csrc/sample.h. */
+int lmi_decode_sample_ex(const float* logits, int B, int vocab, int ld_logits, const int64_t* suppress, int n_suppress, const float* temperature,
+                         const int* top_k, const float* top_p, const float* min_p, const float* typical_p, const float* epsilon_cutoff,
+                         const float* eta_cutoff, const uint64_t* seed, int* step, int64_t* tok, int* pos, int* k_len, int* live, int* budget,
+                         const int64_t* eos, int n_eos, int64_t* hist, int* hist_pos, int hist_len, void* stream);
+
 /* RoPE (rotate-half; cos/sin fp32 [S, head_dim/2] built from position_ids and the llama3-scaled inverse
  * frequencies, rotary_pos_embedding.py:48-83,197-239) applied in place to the q and k heads of packed qkv rows
  * [S, ld]; when k_cache/v_cache are non-null also appends rotated K and V to the cache rows cache_pos0.. */

@@ -99,6 +99,7 @@ SIGNATURES = {
     "lmi_gemm_skinny": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "lmi_decode_advance": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P],
     "lmi_decode_sample": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P],
+    "lmi_decode_sample_ex": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P],
     "lmi_lm_head_last": [_P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "lmi_rmsnorm_rows": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
     "lmi_token_logprobs": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P],

@@ -214,11 +214,11 @@ class LeopardForConditionalGeneration(DecodeBatchLimitOption):
 
     # ---- EVAL:448-452 ------------------------------------------------------------------------------------------
     def _sampling(self, where: str, unused: dict, do_sample, temperature, top_k, top_p, seed, repetition_penalty=None,
-                  no_repeat_ngram_size=None, min_new_tokens=None):
+                  no_repeat_ngram_size=None, min_new_tokens=None, **warpers):
         """HF decoding arguments -> (SamplingParams (None = greedy), LogitsRules (None = no rule)); unsupported options warn
-        (leopard_amd.sampling)."""
+        (leopard_amd.sampling).  ``warpers``: min_p / typical_p / epsilon_cutoff / eta_cutoff of the call."""
         sampling.warn_unsupported(where, unused)
-        sp = sampling.resolve(self.generation_defaults, do_sample, temperature, top_k, top_p, seed)
+        sp = sampling.resolve(self.generation_defaults, do_sample, temperature, top_k, top_p, seed, **warpers)
         rules = sampling.resolve_rules(self.generation_defaults, repetition_penalty, no_repeat_ngram_size, min_new_tokens)
         self.last_decoding = sampling.describe(sp, rules)
         return sp, rules
@@ -227,14 +227,17 @@ class LeopardForConditionalGeneration(DecodeBatchLimitOption):
     def generate(self, input_ids, pixel_values=None, attention_mask=None, pad_token_id=None, eos_token_id=None,
                  max_new_tokens: int = 128, use_cache: bool = True, do_sample=None, temperature=None, top_k=None, top_p=None,
                  seed: Optional[int] = None, logprobs: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None,
-                 min_new_tokens=None, **unused):
-        """Greedy (EVAL:448-452), or sampled with ``do_sample=True`` (temperature / top_k / top_p, HF semantics: leopard_amd.sampling).
+                 min_new_tokens=None, min_p=None, typical_p=None, epsilon_cutoff=None,
+                 eta_cutoff=None, **unused):
+        """Greedy (EVAL:448-452), or sampled with ``do_sample=True`` (temperature / top_k / top_p, then min_p / typical_p / epsilon_cutoff /
+        eta_cutoff, HF semantics and order: leopard_amd.sampling).
         ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens``: HF's logits processors over the ids of ``input_ids`` and the
         generated tokens, inside the decode step (LeopardEngine's LogitsRules); not together with ``logprobs``.
         ``logprobs`` = k in 0 .. 8: returns a ``sampling.GenerationLogprobs`` (.sequences, .token_logprobs, .top_token_ids, .top_logprobs,
         .sequence_logprob) instead of the tensor — computed inside the decode step (LeopardEngine.generate)."""
         sp, rules = self._sampling("generate", unused, do_sample, temperature, top_k, top_p, seed, repetition_penalty, no_repeat_ngram_size,
-                                   min_new_tokens)
+                                   min_new_tokens, min_p=min_p, typical_p=typical_p,
+                                   epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
         if input_ids.shape[0] != 1:
             raise NotImplementedError("batch 1 per call, as in the reference harness")
         tiles = self._as_tiles(pixel_values)
@@ -265,13 +268,15 @@ class LeopardForConditionalGeneration(DecodeBatchLimitOption):
     @torch.no_grad()
     def generate_batch(self, requests: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], eos_token_id=None,
                        max_new_tokens: int = 128, do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None,
-                       logprobs: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, **unused):
+                       logprobs: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None,
+                       min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, **unused):
         """[(input_ids [1, S_in], pixel_values)] -> [LongTensor [1, S_in + T]]: the batched form of ``generate`` (one packed prefill
         for all requests, LeopardEngine.generate_batch).  Not a surface of the reference script — its loop is batch 1 — but of
         leopard_amd.harness.run_inference(batch_size=...).  Sampling: request i draws with its own seed (SamplingParams.for_request).
         ``logprobs`` = k: a list of ``sampling.GenerationLogprobs``, one per request, instead of the tensors."""
         sp, rules = self._sampling("generate_batch", unused, do_sample, temperature, top_k, top_p, seed, repetition_penalty,
-                                   no_repeat_ngram_size, min_new_tokens)
+                                   no_repeat_ngram_size, min_new_tokens, min_p=min_p, typical_p=typical_p,
+                                   epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
         samples = [(ids.to(self.device), self._as_tiles(pix)) for ids, pix in requests]
         out = self.engine.generate_batch(samples, max_new_tokens=max_new_tokens, eos_token_id=_eos_list(eos_token_id), sampling=sp,
                                          logprobs=logprobs, rules=rules)
@@ -281,7 +286,8 @@ class LeopardForConditionalGeneration(DecodeBatchLimitOption):
     @torch.no_grad()
     def generate_shared(self, prefix_ids, pixel_values, suffix_ids_list: Sequence[torch.Tensor], eos_token_id=None, max_new_tokens: int = 128,
                         do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None, decode: str = "copy",
-                        logprobs: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, **unused):
+                        logprobs: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None,
+                        min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, **unused):
         """Many questions about one set of images: ``prefix_ids`` [1, S_p] (the chat head and every image group, with ``pixel_values``) is
         prefilled ONCE — the vision tower runs once — and the text-only ``suffix_ids_list`` ([1, s_j] each: question, instruction, tail)
         continue from its cache together (LeopardEngine.generate_shared).  Returns [LongTensor [1, S_p + s_j + T]], each what ``generate``
@@ -291,7 +297,8 @@ class LeopardForConditionalGeneration(DecodeBatchLimitOption):
         (head_dim 128 and 4 query heads per KV head; NotImplementedError otherwise).  ``logprobs`` = k: a list of
         ``sampling.GenerationLogprobs`` instead of the tensors (ranking the N answers by ``sequence_logprob`` needs no second pass)."""
         sp, rules = self._sampling("generate_shared", unused, do_sample, temperature, top_k, top_p, seed, repetition_penalty,
-                                   no_repeat_ngram_size, min_new_tokens)
+                                   no_repeat_ngram_size, min_new_tokens, min_p=min_p, typical_p=typical_p,
+                                   epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
         out = self.engine.generate_shared(prefix_ids.to(self.device), self._as_tiles(pixel_values), [s.to(self.device) for s in suffix_ids_list],
                                           max_new_tokens=max_new_tokens, eos_token_id=_eos_list(eos_token_id), sampling=sp, decode=decode,
                                           logprobs=logprobs, rules=rules)
@@ -301,13 +308,15 @@ class LeopardForConditionalGeneration(DecodeBatchLimitOption):
     def generate_stream(self, requests: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], batch_size: int = 8, eos_token_id=None,
                         max_new_tokens: int = 128, stats: Optional[dict] = None, do_sample=None, temperature=None, top_k=None, top_p=None,
                         seed: Optional[int] = None, logprobs: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None,
-                        min_new_tokens=None, **unused):
+                        min_new_tokens=None, min_p=None, typical_p=None, epsilon_cutoff=None,
+                        eta_cutoff=None, **unused):
         """Continuous batching over a list of requests: ``batch_size`` decode slots kept busy (LeopardEngine.generate_stream); the outputs
         come back in request order, each what ``generate`` returns for that request.  Sampling: request i draws with its own seed
         (SamplingParams.for_request), so its tokens do not depend on ``batch_size``.  ``logprobs`` = k: a list of
         ``sampling.GenerationLogprobs`` instead of the tensors."""
         sp, rules = self._sampling("generate_stream", unused, do_sample, temperature, top_k, top_p, seed, repetition_penalty,
-                                   no_repeat_ngram_size, min_new_tokens)
+                                   no_repeat_ngram_size, min_new_tokens, min_p=min_p, typical_p=typical_p,
+                                   epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
         # a callable in place of the pixels is called when a slot admits the request (leopard_amd.harness: bounded memory over a shard)
         samples = [(ids.to(self.device), (lambda f=pix: self._as_tiles(f())) if callable(pix) else self._as_tiles(pix)) for ids, pix in requests]
         out = self.engine.generate_stream(samples, batch_size=batch_size, max_new_tokens=max_new_tokens, eos_token_id=_eos_list(eos_token_id),

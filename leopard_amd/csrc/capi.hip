@@ -1832,6 +1832,26 @@ int lmi_decode_sample(const float* logits, int B, int vocab, int ld_logits, cons
     return check_launch("lmi_decode_sample");
 }
 
+int lmi_decode_sample_ex(const float* logits, int B, int vocab, int ld_logits, const int64_t* suppress, int n_suppress, const float* temperature,
+                         const int* top_k, const float* top_p, const float* min_p, const float* typical_p, const float* epsilon_cutoff,
+                         const float* eta_cutoff, const uint64_t* seed, int* step, int64_t* tok, int* pos, int* k_len, int* live, int* budget,
+                         const int64_t* eos, int n_eos, int64_t* hist, int* hist_pos, int hist_len, void* stream) {
+    if (!logits || !tok || !pos || !temperature || !top_k || !top_p || !seed || !step || B < 0 || vocab <= 0 || ld_logits < vocab ||
+        n_suppress < 0 || (n_suppress && !suppress) || n_eos < 0 || (n_eos && !eos) || (hist && (!hist_pos || hist_len <= 0)))
+        return fail(LMI_EINVAL, "lmi_decode_sample_ex: bad argument");
+    if (B == 0) return LMI_OK;
+    DecodeSampleExArgs x;
+    DecodeSampleArgs& a = x.s;
+    DecodeAdvanceArgs& d = a.adv;
+    d.logits = logits; d.vocab = vocab; d.ld_logits = ld_logits; d.suppress = suppress; d.n_suppress = n_suppress; d.tok = tok; d.pos = pos;
+    d.k_len = k_len; d.live = live; d.budget = budget; d.eos = eos; d.n_eos = n_eos; d.hist = hist; d.hist_pos = hist_pos; d.hist_len = hist_len;
+    d.B = B;
+    a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.seed = seed; a.step = step;
+    x.min_p = min_p; x.typical_p = typical_p; x.epsilon_cutoff = epsilon_cutoff; x.eta_cutoff = eta_cutoff;
+    LMI_LAUNCH(decode_sample_ex_kernel, dim3(B), dim3(1024), 0, stream, x);
+    return check_launch("lmi_decode_sample_ex");
+}
+
 int lmi_gemv(const void* W, const void* x, const float* bias, void* out, int N, int K, int ldw, int epilogue, int dtype,
              void* stream) {
     if (!W || !x || !out || N <= 0 || K <= 0 || (K & 7) || (ldw & 7) || K > 28 * 512 || (epilogue == 3 && (N & 63)))

@@ -165,13 +165,31 @@ class KVCache:
 @dataclass
 class SamplingParams:
     """Sampled decoding (lmi_decode_sample, csrc/sample.h): temperature, then top-k (0 = off), then top-p (1.0 = off); the draws of a
-    request are Philox4x32-10 keyed by ``seed``, one counter step per produced token (step 0 = the token from the prefill's logits)."""
+    request are Philox4x32-10 keyed by ``seed``, one counter step per produced token (step 0 = the token from the prefill's logits).
+    Then HF's remaining warpers, in HF's order, each over what the earlier ones left (lmi_decode_sample_ex): ``min_p`` in (0, 1] (0 = off),
+    ``typical_p`` in (0, 1) (1.0 = off), ``epsilon_cutoff`` and ``eta_cutoff`` in (0, 1) (0 = off).  A call with all four off runs
+    lmi_decode_sample."""
     temperature: float = 1.0
     top_k: int = 50
     top_p: float = 1.0
     seed: int = 0
+    min_p: float = 0.0
+    typical_p: float = 1.0
+    epsilon_cutoff: float = 0.0
+    eta_cutoff: float = 0.0
 
     def __post_init__(self):
+        self.min_p = 0.0 if self.min_p is None else float(self.min_p)
+        if not 0.0 <= self.min_p <= 1.0:
+            raise ValueError(f"min_p must be in [0, 1], got {self.min_p}")
+        self.typical_p = float(self.typical_p)
+        if not 0.0 < self.typical_p <= 1.0:
+            raise ValueError(f"typical_p must be in (0, 1], got {self.typical_p}")
+        self.epsilon_cutoff, self.eta_cutoff = float(self.epsilon_cutoff), float(self.eta_cutoff)
+        if not 0.0 <= self.epsilon_cutoff < 1.0:
+            raise ValueError(f"epsilon_cutoff must be in [0, 1), got {self.epsilon_cutoff}")
+        if not 0.0 <= self.eta_cutoff < 1.0:
+            raise ValueError(f"eta_cutoff must be in [0, 1), got {self.eta_cutoff}")
         if not self.temperature > 0:
             raise ValueError(f"temperature must be > 0 when sampling, got {self.temperature}")
         if int(self.top_k) < 0:
@@ -182,10 +200,19 @@ class SamplingParams:
 
     def for_request(self, i: int) -> "SamplingParams":
         """The parameters of request i of a call: its seed depends on the call's seed and i only (not on batch size or admission order)."""
-        return SamplingParams(self.temperature, self.top_k, self.top_p, (self.seed + i * 0x9E3779B97F4A7C15) & ((1 << 64) - 1))
+        return SamplingParams(self.temperature, self.top_k, self.top_p, (self.seed + i * 0x9E3779B97F4A7C15) & ((1 << 64) - 1),
+                              self.min_p, self.typical_p, self.epsilon_cutoff, self.eta_cutoff)
+
+    @property
+    def extended(self) -> bool:
+        """Any of min_p / typical_p / epsilon_cutoff / eta_cutoff is on: the step draws with lmi_decode_sample_ex."""
+        return self.min_p > 0.0 or self.typical_p < 1.0 or self.epsilon_cutoff > 0.0 or self.eta_cutoff > 0.0
 
     def describe(self) -> str:
-        return f"sample(temperature={self.temperature:g}, top_k={int(self.top_k)}, top_p={self.top_p:g})"
+        more = "".join(f", {name}={v:g}" for name, v, off in (("min_p", self.min_p, 0.0), ("typical_p", self.typical_p, 1.0),
+                                                             ("epsilon_cutoff", self.epsilon_cutoff, 0.0),
+                                                             ("eta_cutoff", self.eta_cutoff, 0.0)) if v != off)
+        return f"sample(temperature={self.temperature:g}, top_k={int(self.top_k)}, top_p={self.top_p:g}{more})"
 
 
 @dataclass(frozen=True)
@@ -268,11 +295,13 @@ class DecodeState:
     topp: torch.Tensor
     seed: torch.Tensor
     step: torch.Tensor
+    ext: torch.Tensor                            # fp32 [4, B]: min_p, typical_p, epsilon_cutoff, eta_cutoff (lmi_decode_sample_ex), one buffer
     # generate(logprobs=k): the rings lmi_decode_logprobs writes after the choice kernel — ONE buffer of 4-byte words, so that the host
     # drains all three with one copy: lp fp32 [ring, B], top_id int32 [ring, B, 8], top_lp fp32 [ring, B, 8] are views of it.  ring = HIST
     # for the pooled states (slot = the step's place in the token history ring), 1 for the batch-1 state (read every step, with the token).
     # Allocated by the first call with ``logprobs`` (_set_logprobs): a state that never sees one holds what it held before
     sampling: bool = False
+    sample_ex: bool = False                      # the running call has one of the four warpers of ``ext`` on: the step draws with _ex
     lp_buf: Optional[torch.Tensor] = None
     lp: Optional[torch.Tensor] = None
     top_id: Optional[torch.Tensor] = None
@@ -308,7 +337,7 @@ class DecodeState:
     beam_id_chunks: Optional[torch.Tensor] = None  # int32 [2]: the chunk that holds the first generated id, the chunks a finished call holds
     # the captured steps (LeopardEngine._run_step), keyed by (sampling, with logprobs): greedy / sampled, each without and with the logprobs
     # launch — the latter two with top_k = lp_k — and by (sampling, False, True) for the steps with the rules launch; a beam step adds
-    # ("beams", K, reorder bound) to its key, without and with rules
+    # ("beams", K, reorder bound) to its key, without and with rules; a sampled step that draws with lmi_decode_sample_ex adds "ex"
     graphs: dict = field(default_factory=dict)
     lp_k: Optional[int] = None                   # the top_k the two logprobs graphs were captured with (another k captures them again)
     graph_failed: bool = False                   # tensor parallel: the capture failed once, the step runs eagerly (_decode_run)
@@ -1734,7 +1763,8 @@ class LeopardEngine:
             ws=torch.empty(ws_elems, dtype=torch.float32, device=dev),
             temp=torch.ones(B, dtype=torch.float32, device=dev), topk=torch.zeros(B, dtype=torch.int32, device=dev),
             topp=torch.ones(B, dtype=torch.float32, device=dev), seed=torch.zeros(B, dtype=torch.int64, device=dev),
-            step=torch.zeros(B, dtype=torch.int32, device=dev))
+            step=torch.zeros(B, dtype=torch.int32, device=dev),
+            ext=torch.tensor([0.0, 1.0, 0.0, 0.0], dtype=torch.float32).repeat(B, 1).t().contiguous().to(dev))
 
     def _decode_state(self, cache: KVCache) -> DecodeState:
         st = cache._decode_state
@@ -1806,6 +1836,8 @@ class LeopardEngine:
         st.temp[j:j + 1].copy_(vals[0:1]); st.topp[j:j + 1].copy_(vals[1:2])
         st.topk[j:j + 1].copy_(ints[0:1]); st.step[j:j + 1].copy_(ints[1:2])
         st.seed[j:j + 1].copy_(torch.tensor([_signed64(sp.seed)], dtype=torch.int64))
+        if st.sample_ex:                                              # (a call without the four warpers never reads them: nothing more is written)
+            st.ext[:, j:j + 1].copy_(torch.tensor([[sp.min_p], [sp.typical_p], [sp.epsilon_cutoff], [sp.eta_cutoff]], dtype=torch.float32))
 
     def _choose(self, st, logits, **kw) -> None:
         """The tail of a decode step: lmi_decode_advance (greedy) or lmi_decode_sample (st.sampling) — the only difference between the two
@@ -1828,7 +1860,10 @@ class LeopardEngine:
         if st.rules:                                                  # generate(rules=...): one more launch, before the choice (it rewrites the rows)
             self.ops.decode_rules(logits, V, st.seq, st.seq_len, st.rule_pen, st.rule_ngram, st.rule_min_left, tok=st.tok, live=kw.get("live"),
                                   eos=st.rule_eos)
-        if st.sampling:
+        if st.sampling and st.sample_ex:                              # min_p / typical_p / epsilon_cutoff / eta_cutoff after top-p
+            self.ops.decode_sample_ex(logits, V, st.temp, st.topk, st.topp, st.seed, st.step, st.tok, st.pos, *st.ext,
+                                      suppress=self.suppress_tokens, **kw)
+        elif st.sampling:
             self.ops.decode_sample(logits, V, st.temp, st.topk, st.topp, st.seed, st.step, st.tok, st.pos, suppress=self.suppress_tokens, **kw)
         else:
             self.ops.decode_advance(logits, V, st.tok, st.pos, suppress=self.suppress_tokens, **kw)
@@ -1907,6 +1942,13 @@ class LeopardEngine:
         return rows
 
     # ---- generate(logprobs=k): the host side ----
+    def _sampling_arg(self, what: str, sampling: Optional["SamplingParams"]) -> Optional["SamplingParams"]:
+        """Validate ``sampling`` before anything is launched: the four warpers of lmi_decode_sample_ex need a single-rank engine."""
+        if sampling is not None and sampling.extended and self.tp_size > 1:
+            raise NotImplementedError(f"{what}: min_p / typical_p / epsilon_cutoff / eta_cutoff are not supported on tensor-parallel engines "
+                                      f"(got {sampling.describe()})")
+        return sampling
+
     def _logprobs_arg(self, what: str, logprobs: Optional[int]) -> Optional[int]:
         """Validate ``logprobs`` before anything is launched: None, or k in 0 .. 8 on a single-rank engine."""
         if logprobs is None:
@@ -1986,7 +2028,7 @@ class LeopardEngine:
 
     def sample_first(self, logits: torch.Tensor, params: Sequence["SamplingParams"]) -> List[int]:
         """The first token of each request from its prefill logits row ([n, >= vocab] or [vocab]) through lmi_decode_sample at step 0
-        (the sampled counterpart of ``first_token``)."""
+        (the sampled counterpart of ``first_token``), through lmi_decode_sample_ex when a request has one of its four warpers on."""
         rows = logits.reshape(-1, logits.shape[-1]).float()
         n, dev = rows.shape[0], rows.device
         temp = torch.tensor([float(p.temperature) for p in params], dtype=torch.float32).to(dev)
@@ -1996,8 +2038,13 @@ class LeopardEngine:
         step = torch.zeros(n, dtype=torch.int32, device=dev)
         tok = torch.zeros(n, dtype=torch.int64, device=dev)
         pos = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.ops.decode_sample(rows, min(self.cfg.text_config.vocab_size, rows.shape[1]), temp, topk, topp, seed, step, tok, pos,
-                               suppress=self.suppress_tokens)
+        V = min(self.cfg.text_config.vocab_size, rows.shape[1])
+        if any(p.extended for p in params):
+            ext = torch.tensor([[p.min_p for p in params], [p.typical_p for p in params], [p.epsilon_cutoff for p in params],
+                                [p.eta_cutoff for p in params]], dtype=torch.float32).to(dev)
+            self.ops.decode_sample_ex(rows, V, temp, topk, topp, seed, step, tok, pos, *ext, suppress=self.suppress_tokens)
+        else:
+            self.ops.decode_sample(rows, V, temp, topk, topp, seed, step, tok, pos, suppress=self.suppress_tokens)
         return [int(t) for t in tok.tolist()]
 
     def _run_step(self, st, body, restore: tuple, capturable: bool = True) -> None:
@@ -2008,7 +2055,7 @@ class LeopardEngine:
         if self.ops.emulated or self.device.type != "cuda" or not self.use_graphs or not capturable:
             body()
             return
-        key = (st.sampling, st.logprobs is not None) + ((True,) if st.rules else ()) + ((("beams", st.beams, st.beam_max_rows),) if st.beams else ())
+        key = (st.sampling, st.logprobs is not None) + ((True,) if st.rules else ()) + (("ex",) if st.sampling and st.sample_ex else ()) + ((("beams", st.beams, st.beam_max_rows),) if st.beams else ())
         if key not in st.graphs:
             # (a beam step is first captured at the first step of a call, where no slot holds a row that can differ yet: the one row the
             # warm-up run appends and permutes is written again by the replay)
@@ -2068,7 +2115,7 @@ class LeopardEngine:
     def decode_step(self, token_id: int, cache: KVCache) -> torch.Tensor:
         """Append one token: returns its logits [vocab] (fp32, a view of a static buffer) and advances the cache."""
         st = self._decode_state(cache)
-        st.sampling, st.logprobs, st.rules, st.beams = False, None, False, 0      # raw logits: never rules
+        st.sampling, st.sample_ex, st.logprobs, st.rules, st.beams = False, False, None, False, 0      # raw logits: never rules
         self._decode_seed(st, cache, token_id)
         self._decode_run(st, cache)
         cache.length += 1
@@ -2101,6 +2148,7 @@ class LeopardEngine:
         out, nxt = list(prompt_ids), int(first)
         st = self._decode_state(cache)
         st.sampling, st.beams = sampling is not None, 0
+        st.sample_ex = sampling is not None and sampling.extended
         self._set_logprobs(st, None if lpr is None else lpr.k)
         self._set_rules(st, rules, eos)
         if rules is not None:
@@ -2142,6 +2190,7 @@ class LeopardEngine:
         counts as its id) and the generated tokens, applied inside the step before the choice (lmi_decode_rules), the first token included.
         Not with ``logprobs``, not on tensor-parallel engines (NotImplementedError, before anything is launched)."""
         k = self._logprobs_arg("generate", logprobs)
+        sampling = self._sampling_arg("generate", sampling)
         rules = self._rules_arg("generate", rules, k, eos_token_id)
         ids = input_ids.reshape(1, -1)
         S = self.merged_len(ids)
@@ -2425,6 +2474,7 @@ class LeopardEngine:
         st.k_len.copy_(torch.tensor([s + 1 for s in (own_lens or seq_lens)], dtype=torch.int32))
         st.live.fill_(1); st.budget.fill_(1 << 30); st.eos.fill_(-1); st.hist_pos.zero_()      # the host applies the stop rule here
         st.sampling, st.beams = sampling is not None, 0
+        st.sample_ex = any(sp.extended for sp in sampling or ())
         self._set_logprobs(st, None if lpr is None else lpr[0].k)
         self._set_rules(st, rules, eos)
         if rules is not None:
@@ -2486,6 +2536,7 @@ class LeopardEngine:
         the token table.  ``rules``: as ``generate``, one value for every request of the call; a slot's ids and countdown are set when it
         admits a request."""
         k = self._logprobs_arg("generate_stream", logprobs)
+        sampling = self._sampling_arg("generate_stream", sampling)
         rules = self._rules_arg("generate_stream", rules, k, eos_token_id)
         assert self.tp_size == 1, "batched generation is a single-rank feature (replicas scale it out)"
         B = max(1, min(int(batch_size), self.decode_batch_limit, len(samples)))
@@ -2502,6 +2553,7 @@ class LeopardEngine:
             st.eos[:len(eos)].copy_(torch.tensor(eos, dtype=torch.int64))
         st.live.zero_(); st.budget.zero_(); st.pos.zero_(); st.k_len.fill_(1); st.tok.zero_(); st.hist_pos.zero_()
         st.sampling, st.beams = sampling is not None, 0
+        st.sample_ex = sampling is not None and sampling.extended
         self._set_logprobs(st, k)
         self._set_rules(st, rules, eos)
         lpr = None if k is None else [None] * len(samples)          # a request's rows start with its first token's (admit)
@@ -2596,6 +2648,7 @@ class LeopardEngine:
         ``logprobs`` = k in 0 .. 8: returns a ``GenerateOutput`` (``sequences`` = that list); the rings are drained once per HIST steps.
         ``rules``: as ``generate``, one value for every request of the call."""
         k = self._logprobs_arg("generate_batch", logprobs)
+        sampling = self._sampling_arg("generate_batch", sampling)
         rules = self._rules_arg("generate_batch", rules, k, eos_token_id)
         assert self.tp_size == 1, "batched generation is a single-rank feature (replicas scale it out)"
         # more samples than one step decodes (decode_batch_limit; 16 where the shape has no batched decode): one call per group
@@ -2960,6 +3013,7 @@ class LeopardEngine:
         the tokens after its suffix.
         ``rules``: as ``generate``, in both ``decode`` modes and on the batch-1 paths; a request's ids are ``prefix_ids`` + its suffix."""
         k = self._logprobs_arg("generate_shared", logprobs)
+        sampling = self._sampling_arg("generate_shared", sampling)
         rules = self._rules_arg("generate_shared", rules, k, eos_token_id)
         if decode not in ("copy", "shared"):
             raise ValueError(f"generate_shared: decode must be 'copy' or 'shared', got {decode!r}")
@@ -3036,7 +3090,7 @@ class LeopardEngine:
             st.beam_row0 = torch.zeros(1, dtype=torch.int32, device=dev)
             st.beam_held = torch.zeros(1, dtype=torch.int32, device=dev)
             st.beam_ptrs = torch.tensor([t.data_ptr() for t in st.k + st.v], dtype=torch.int64).to(dev)
-        st.beams, st.sampling = K, False
+        st.beams, st.sampling, st.sample_ex = K, False, False
         st.beam_max_rows = (max_new_tokens + 255) // 256 * 256
         self._set_logprobs(st, None)
         self._set_rules(st, rules, eos)

@@ -278,15 +278,17 @@ class Idefics2ForConditionalGeneration(DecodeBatchLimitOption):
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, pixel_values=None, pixel_attention_mask=None, max_new_tokens: int = 128,
                  eos_token_id=None, do_sample=None, temperature=None, top_k=None, top_p=None, seed: Optional[int] = None,
-                 logprobs: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, **unused):
-        """Greedy, or sampled with ``do_sample=True`` (HF semantics, generation_config.json defaults: leopard_amd.sampling).
+                 logprobs: Optional[int] = None, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, min_p=None,
+                 typical_p=None, epsilon_cutoff=None, eta_cutoff=None, **unused):
+        """Greedy, or sampled with ``do_sample=True`` (HF semantics, generation_config.json defaults: leopard_amd.sampling; ``min_p`` /
+        ``typical_p`` / ``epsilon_cutoff`` / ``eta_cutoff`` follow top-p in HF's order).
         ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens``: HF's logits processors inside the decode step (LeopardEngine's
         LogitsRules; the ids seen are ``input_ids`` as passed, then the generated tokens); not together with ``logprobs``.
         ``logprobs`` = k in 0 .. 8: returns a ``sampling.GenerationLogprobs`` instead of the tensor (raw-logit log-softmax values: an id of
         ``suppress_tokens`` may appear among ``top_token_ids``, never as the generated token)."""
         k = self.engine._logprobs_arg("generate", logprobs)
         sampling.warn_unsupported("generate", unused)
-        sp = sampling.resolve(self.generation_defaults, do_sample, temperature, top_k, top_p, seed)
+        sp = sampling.resolve(self.generation_defaults, do_sample, temperature, top_k, top_p, seed, min_p, typical_p, epsilon_cutoff, eta_cutoff)
         rules = sampling.resolve_rules(self.generation_defaults, repetition_penalty, no_repeat_ngram_size, min_new_tokens)
         self.last_decoding = sampling.describe(sp, rules)
         if input_ids.shape[0] != 1:

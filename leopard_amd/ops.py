@@ -466,6 +466,21 @@ class Ops:
                                                _ptr(tok), _ptr(pos), _ptr(k_len), _ptr(live), _ptr(budget), _ptr(eos), 0 if eos is None else eos.numel(),
                                                _ptr(hist), _ptr(hist_pos), 0 if hist is None else hist.shape[0], self._stream(logits)))
 
+    def decode_sample_ex(self, logits, vocab, temperature, top_k, top_p, seed, step, tok, pos, min_p=None, typical_p=None, epsilon_cutoff=None,
+                         eta_cutoff=None, k_len=None, live=None, budget=None, eos=None, hist=None, hist_pos=None, suppress=None):
+        """lmi_decode_sample_ex: decode_sample followed by HF's remaining warpers, in HF's order — ``min_p`` (0 = off), ``typical_p``
+        (1 = off), ``epsilon_cutoff`` (0 = off), ``eta_cutoff`` (0 = off): fp32 device tensors of length B, or None (off for every row)."""
+        B = logits.shape[0]
+        for t, dt in ((temperature, torch.float32), (top_k, torch.int32), (top_p, torch.float32), (seed, torch.int64), (step, torch.int32),
+                      (min_p, torch.float32), (typical_p, torch.float32), (epsilon_cutoff, torch.float32), (eta_cutoff, torch.float32)):
+            if t is not None and (t.dtype != dt or t.numel() < B):
+                raise TypeError(f"leopard_amd: decode_sample_ex parameter must be {dt} with >= {B} entries, got {t.dtype} [{t.numel()}]")
+        self._check(self.lib.lmi_decode_sample_ex(_ptr(logits), B, int(vocab), logits.stride(0), _ptr(suppress), 0 if suppress is None else suppress.numel(),
+                                                  _ptr(temperature), _ptr(top_k), _ptr(top_p), _ptr(min_p), _ptr(typical_p), _ptr(epsilon_cutoff),
+                                                  _ptr(eta_cutoff), _ptr(seed), _ptr(step),
+                                                  _ptr(tok), _ptr(pos), _ptr(k_len), _ptr(live), _ptr(budget), _ptr(eos), 0 if eos is None else eos.numel(),
+                                                  _ptr(hist), _ptr(hist_pos), 0 if hist is None else hist.shape[0], self._stream(logits)))
+
     def decode_workspace_elems(self, q_rows, n_heads, head_dim, max_seqlen_k) -> int:
         n = int(self.lib.lmi_attn_decode_workspace_bytes(q_rows, n_heads, head_dim, max_seqlen_k))
         if n < 0:

@@ -3,8 +3,9 @@
 HF semantics: ``do_sample`` False or absent = greedy (bit-identical to the greedy path); with ``do_sample=True`` an argument left unset
 takes the checkpoint's generation_config.json value, else HF's default (temperature 1.0, top_k 50, top_p 1.0); ``temperature <= 0``
 with sampling raises ValueError.  The per-call seed comes from torch's default CPU generator (``torch.manual_seed(s)`` makes a run
-reproducible) unless ``seed=`` is passed.  Options this library does not implement (beam search, penalties, min-p, ...) produce one
-warning naming them instead of being ignored silently.  ``repetition_penalty``, ``no_repeat_ngram_size`` and ``min_new_tokens`` are
+reproducible) unless ``seed=`` is passed.  ``min_p``, ``typical_p``, ``epsilon_cutoff`` and ``eta_cutoff`` are HF's warpers after top-p, in HF's order (lmi_decode_sample_ex): call
+arguments over generation_config.json over "off"; ignored, as ``temperature``, without ``do_sample``.  Options this library does not
+implement (``penalty_alpha``, ``num_return_sequences``, ...) produce one warning naming them instead of being ignored silently.  ``repetition_penalty``, ``no_repeat_ngram_size`` and ``min_new_tokens`` are
 implemented (LeopardEngine's LogitsRules): call arguments over generation_config.json over "off" (``resolve_rules``)."""
 from __future__ import annotations
 
@@ -19,13 +20,14 @@ import torch
 from .engine import GenerateOutput, LogitsRules, SamplingParams
 
 HF_DEFAULTS = {"temperature": 1.0, "top_k": 50, "top_p": 1.0}
-SAMPLING_KEYS = ("do_sample", "temperature", "top_k", "top_p")
+WARPER_OFF = {"min_p": 0.0, "typical_p": 1.0, "epsilon_cutoff": 0.0, "eta_cutoff": 0.0}     # lmi_decode_sample_ex: implemented; the value = off
+SAMPLING_KEYS = ("do_sample", "temperature", "top_k", "top_p") + tuple(WARPER_OFF)
 RULE_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens")       # LogitsRules: implemented (lmi_decode_rules)
 BEAM_KEYS = ("num_beams", "length_penalty", "early_stopping")                     # generate_beams: implemented (lmi_beam_step)
 BEAM_DEFAULTS = {"num_beams": 1, "length_penalty": 1.0, "early_stopping": False}  # HF's
-# generate() options that change the decoding rule and are not implemented, with the value that means "off".  The three RULE_KEYS are still
-# listed — warn_unsupported names whatever it is handed — but the generate() surfaces take them as named parameters (``resolve_rules``),
-# so they never reach it from there and no longer warn
+# generate() options that change the decoding rule and are not implemented, with the value that means "off".  The three RULE_KEYS and the
+# four warpers of WARPER_OFF are still listed — warn_unsupported names whatever it is handed — but the generate() surfaces take them as
+# named parameters (``resolve_rules``, ``resolve``), so they never reach it from there and no longer warn
 UNSUPPORTED = {"num_beams": 1, "num_beam_groups": 1, "penalty_alpha": None, "repetition_penalty": 1.0, "encoder_repetition_penalty": 1.0,
                "length_penalty": 1.0, "no_repeat_ngram_size": 0, "min_p": None, "typical_p": 1.0, "epsilon_cutoff": 0.0,
                "eta_cutoff": 0.0, "num_return_sequences": 1, "diversity_penalty": 0.0, "sequence_bias": None, "guidance_scale": None,
@@ -63,8 +65,9 @@ def warn_unsupported(where: str, kwargs: dict) -> None:
 
 
 def resolve(defaults: Optional[dict] = None, do_sample=None, temperature=None, top_k=None, top_p=None,
-            seed: Optional[int] = None) -> Optional[SamplingParams]:
-    """None = greedy; otherwise the SamplingParams of this call (call arguments over ``defaults`` over HF's defaults)."""
+            seed: Optional[int] = None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> Optional[SamplingParams]:
+    """None = greedy; otherwise the SamplingParams of this call (call arguments over ``defaults`` over HF's defaults; the four warpers after
+    top-p: over "off").  Values outside their ranges raise ValueError (SamplingParams)."""
     d = defaults or {}
     if not bool(do_sample if do_sample is not None else d.get("do_sample", False)):
         return None
@@ -75,7 +78,9 @@ def resolve(defaults: Optional[dict] = None, do_sample=None, temperature=None, t
         raise ValueError(f"`temperature` (={t}) has to be a strictly positive float when sampling")
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())        # torch's default CPU generator: torch.manual_seed(s) reproduces the run
-    return SamplingParams(float(t), int(k), float(p), int(seed))
+    more = {"min_p": min_p, "typical_p": typical_p, "epsilon_cutoff": epsilon_cutoff, "eta_cutoff": eta_cutoff}
+    more = {key: v if v is not None else (d[key] if d.get(key) is not None else off) for (key, off), v in zip(WARPER_OFF.items(), more.values())}
+    return SamplingParams(float(t), int(k), float(p), int(seed), **more)
 
 
 def resolve_rules(defaults: Optional[dict] = None, repetition_penalty=None, no_repeat_ngram_size=None,
